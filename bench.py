@@ -3,9 +3,15 @@
 
 Primary line (N=1 default): config 2 — ORDER BY int64 key on 1B rows x 3 cols
 (int64 key, int64, float64) on one MI355X, whole-operator rows/s with inputs
-resident in HBM. Sub-benchmarks in the same JSON line: config 3 (GROUP BY
-1B rows / 10M groups, SUM float64) and config 4 scaled per GPU (shuffled hash
-join, 0.5B rows/side/GPU; at N>1 the real RCCL all-to-all exchange runs).
+resident in HBM. A plain run does that and nothing else: set up, warm up,
+time --steps steps, print one JSON line. --dump-outputs DIR also writes what
+the last timed step produced (seeded sample, float64 .npy) so two builds can
+be compared output for output.
+
+--full adds, in the same JSON line, the sub-benchmarks — config 3 (GROUP BY
+1B rows / 10M groups, SUM float64), config 4 scaled per GPU (shuffled hash
+join, 0.5B rows/side/GPU; at N>1 the real RCCL all-to-all exchange runs) and
+the config-5 Q1/Q3 plans — and the CPU baseline.
 
 N>1 (launched by the driver via torch.distributed.run): sort and agg run as
 independent per-rank batches (weak scaling — config 2/3 are single-partition
@@ -478,6 +484,44 @@ def time_workload(w, steps, warmup, world):
     return dt / steps
 
 
+DUMP_SAMPLE_ROWS = 1 << 20   # 6 float64 arrays x 8 MiB = 48 MiB <= the 64 MB cap
+DUMP_SAMPLE_SEED = 20260
+
+
+def _save_i64_split(path_stem, t):
+    """int64 (full-range) does not fit float64's 53-bit mantissa: store the
+    signed high and unsigned low 32-bit halves, each exact in float64
+    (value = hi * 2**32 + lo)."""
+    import numpy as np
+    a = t.cpu().numpy()
+    np.save(path_stem + "_hi.npy", (a >> 32).astype(np.float64))
+    np.save(path_stem + "_lo.npy", (a & 0xFFFFFFFF).astype(np.float64))
+
+
+def dump_sort_outputs(w, out_dir):
+    """What the timed sort step handed back in its last step — the
+    permutation, the sorted keys and both gathered payload columns — at a
+    fixed seeded sample of output positions (all of them when the output is
+    no larger than the sample), one float64 .npy per array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if w.rows <= DUMP_SAMPLE_ROWS:
+        pos = np.arange(w.rows, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(
+            0, w.rows, DUMP_SAMPLE_ROWS, dtype=np.int64))
+    torch.cuda.synchronize()
+    idx = torch.from_numpy(pos).cuda()
+    # row ids are u32 carried in an int32 tensor
+    rid = w.perm[idx].to(torch.int64) & 0xFFFFFFFF
+    np.save(os.path.join(out_dir, "sort_perm.npy"),
+            rid.cpu().numpy().astype(np.float64))
+    _save_i64_split(os.path.join(out_dir, "sort_keys"), w.skeys[idx])
+    _save_i64_split(os.path.join(out_dir, "sort_payload_i64"), w.out1[idx])
+    np.save(os.path.join(out_dir, "sort_payload_f64.npy"),
+            w.out2[idx].cpu().numpy())
+
+
 def cpu_baseline_sort(sample_rows):
     """Oracle (C restatement) on the same sort workload shape, OpenMP
     multithreaded (the substitute leg BASELINE.md specifies). The thread
@@ -518,8 +562,26 @@ def main():
     p.add_argument("--quick", action="store_true", help="small sizes (CI/sanity)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-sample-rows", type=int, default=40_000_000)
-    p.add_argument("--workloads", default="sort,agg,join,q1,q3,gsort")
+    p.add_argument("--full", action="store_true",
+                   help="also run the sub-benchmarks (agg, join, q1, q3, and "
+                        "gsort at N>1) and the CPU-oracle baseline; a plain "
+                        "run times the headline sort workload only")
+    p.add_argument("--workloads", default=None,
+                   help="with --full: which workloads to run "
+                        "(default sort,agg,join,q1,q3,gsort)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last sort step "
+                        "produced as DIR/<name>.npy (float64, seeded sample)")
     args = p.parse_args()
+    if args.full:
+        args.workloads = args.workloads or "sort,agg,join,q1,q3,gsort"
+    elif args.workloads is not None:
+        p.error("--workloads needs --full")
+    else:
+        args.workloads = "sort"
+        args.no_cpu_baseline = True
+    if args.dump_outputs and "sort" not in args.workloads.split(","):
+        p.error("--dump-outputs writes the sort workload's outputs")
     if args.quick:
         args.rows, args.agg_rows, args.agg_groups, args.join_rows = \
             20_000_000, 20_000_000, 200_000, 10_000_000
@@ -551,6 +613,8 @@ def main():
             sec = time_workload(w, args.steps, args.warmup, world)
             scat_ms, scat_n = gq.kernel_stats("radix_scatter")
             hist_ms, hist_n = gq.kernel_stats("radix_hist")
+            if args.dump_outputs and rank == 0:
+                dump_sort_outputs(w, args.dump_outputs)
             w.free()
             torch.cuda.empty_cache()
             results["sort"] = {

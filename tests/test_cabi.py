@@ -4,7 +4,9 @@ in a GPU-less container, and exports every symbol include/gpuq.h declares
 import ctypes
 import os
 import re
+import shutil
 import subprocess
+import tempfile
 
 import pytest
 
@@ -48,9 +50,16 @@ def test_so_loads_and_exports_all_header_symbols():
 
 def test_so_is_gfx950_only():
     _ensure_built()
-    out = subprocess.run(
-        ["/opt/rocm/lib/llvm/bin/llvm-objdump", "--offloading", SO],
-        capture_output=True, text=True)
+    # llvm-objdump --offloading extracts each bundle entry to a file next to
+    # its input: run it on a throw-away copy (by relative name, so the
+    # directory's name cannot reach the output) to keep the tree clean
+    with tempfile.TemporaryDirectory() as tmp:
+        shutil.copy(SO, os.path.join(tmp, "libgpuq.so"))
+        out = subprocess.run(
+            [os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"),
+                          "lib", "llvm", "bin", "llvm-objdump"),
+             "--offloading", "libgpuq.so"],
+            capture_output=True, text=True, cwd=tmp)
     blob = out.stdout + out.stderr
     if "gfx" in blob:
         assert "gfx950" in blob
