@@ -182,7 +182,7 @@ int gpuq_hash_agg_partitioned(void* stream, int64_t nrows,
                               double* out_sums, uint8_t* out_sum_valid,
                               int64_t* out_counts, int64_t* out_ngroups);
 
-/* Multi-aggregate: one pass computing up to 6 accumulators per group
+/* Multi-aggregate: one pass computing up to 12 accumulator words per group
  * (HashAggregateExec evaluates a list of aggregate expressions,
  * HashAggregateExec.scala:68-76 — e.g. TPC-H Q1's 8 aggregates).
  * spec_ops[j]: 0=SUM(float64 col), 1=COUNT(col), 2=COUNT(*),
@@ -196,7 +196,24 @@ int gpuq_hash_agg_partitioned(void* stream, int64_t nrows,
  * first. Value ops skip NULL rows; an all-NULL group emits the op's
  * neutral init (0 for SUM/COUNT, extremes for MIN/MAX) — pair with a
  * COUNT spec to realize SQL NULL results (Sum.scala: NULL iff no
- * non-null input). */
+ * non-null input).
+ *
+ * Exact decimal SUM (Sum.scala's Decimal path for decimal(p<=18,s) carried
+ * as scaled int64; result decimal(min(38,p+10),s)): a 128-bit accumulator
+ * held in TWO adjacent specs, so each decimal sum costs 2 of the 12 specs.
+ *   8=SUM_DEC128(int64 col): the lo word; must be followed immediately by 9.
+ *   9=DEC128_HI: the hi word of the preceding spec (8 or 10); its own
+ *     update is a no-op. After op 8 its spec_cols entry is ignored.
+ *  10=MERGE_DEC128: final-mode merge of 128-bit partials; spec_cols[j] is
+ *     the partial lo column (int64 bits) and the following op 9's
+ *     spec_cols[j+1] is the partial hi column (int64).
+ * out_accs[j] receives lo as int64 bits and out_accs[j+1] hi as signed
+ * int64: value = (hi << 64) | (uint64)lo, two's complement, wrapping only
+ * at 2^127. NULL rows are skipped by the validity bitmap of the op-8 column
+ * (op 10: of the partial lo column); an all-NULL group emits (0, 0) — pair
+ * with a COUNT spec as for the other ops. A pairing violation (8/10 last or
+ * not followed by 9, 9 not preceded by 8/10) or a non-int64 column returns
+ * GPUQ_ERR_INVALID before anything is launched. */
 int64_t gpuq_hash_agg_multi_workspace_bytes(int64_t capacity, int32_t nspecs);
 int gpuq_hash_agg_multi(void* stream, int64_t nrows, gpuq_col key,
                         const gpuq_col* vals, const int32_t* spec_ops,
@@ -378,6 +395,14 @@ int gpuq_maskbit_to_bits(void* stream, int64_t nrows, const uint8_t* mask,
  * SUM/MIN/MAX results (final-mode aggregation, Sum.scala merge) */
 int gpuq_nonzero_to_bits(void* stream, int64_t nrows, const int64_t* in,
                          uint8_t* out_bits);
+
+/* Decimal-overflow-to-NULL for 128-bit sums (Sum.scala, non-ANSI): clears
+ * validity bit i (Arrow LSB order, in/out) when |(hi[i],lo[i])| >=
+ * 10^result_precision, 1 <= result_precision <= 38; bits already clear stay
+ * clear. (lo, hi) as emitted by spec ops 8/9/10 above. */
+int gpuq_dec128_overflow_to_null(void* stream, int64_t nrows, const int64_t* lo,
+                                 const int64_t* hi, int32_t result_precision,
+                                 uint8_t* validity_bits);
 
 /* min/max/valid-count reduction of an int64 column. out_dev: device u64[3]
  * = {min encoded (encode_i64), max encoded, count of valid rows}. */

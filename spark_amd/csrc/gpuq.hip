@@ -2973,7 +2973,13 @@ struct agg_cols { const double* p[AGG_MAX_SPECS]; };
  * realize the reference ordering incl. NaN-greatest and -0.0 < 0.0; the
  * compact pass decodes. All value ops skip NULL rows; an all-NULL group's
  * acc stays at its init value — callers discriminate via a paired COUNT
- * (Sum/Min/Max evaluate to NULL iff no non-null input). */
+ * (Sum/Min/Max evaluate to NULL iff no non-null input).
+ * 8=SUM_DEC128 9=DEC128_HI 10=MERGE_DEC128: exact 128-bit SUM of scaled-
+ * decimal int64 values (Sum.scala's Decimal path, result
+ * decimal(min(38,p+10),s)). The accumulator is TWO adjacent words (lo, hi):
+ * op 8/10 owns word j and must be followed by op 9 owning word j+1, so a
+ * decimal sum costs two of the AGG_MAX_SPECS slots. Both words init to 0,
+ * so strides, init, compaction and emit are untouched. */
 struct agg_ops_spec { int op[AGG_MAX_SPECS]; };
 struct agg_valid { const uint8_t* v[AGG_MAX_SPECS]; };
 struct agg_outs { void* p[AGG_MAX_SPECS]; };
@@ -3048,6 +3054,21 @@ DEV void aggm_update(unsigned long long* acc, int nspecs, const agg_ops_spec ops
     } else if (op == 4 || op == 5) {
       unsigned long long e = encode_i64(((const int64_t*)cols.p[j])[i]);
       if (op == 4) atomicMin(&acc[j], e); else atomicMax(&acc[j], e);
+    } else if (op == 8 || op == 10) {
+      /* 128-bit two's-complement add into (acc[j], acc[j+1]). op 8 sign-
+       * extends an int64 value; op 10 adds a 128-bit partial whose hi word
+       * is op 9's column. Every wrap of lo is observed by exactly one
+       * returning atomic, which forwards that carry to hi — so the pair is
+       * the exact sum in any arrival order, with no CAS loop. */
+      unsigned long long add_lo = (unsigned long long)((const int64_t*)cols.p[j])[i];
+      unsigned long long add_hi = op == 8
+          ? ((long long)add_lo < 0 ? ~0ULL : 0ULL)
+          : (unsigned long long)((const int64_t*)cols.p[j + 1])[i];
+      unsigned long long old = atomicAdd(&acc[j], add_lo);
+      add_hi += (old + add_lo) < old;
+      if (add_hi) atomicAdd(&acc[j + 1], add_hi);
+    } else if (op == 9) {
+      /* DEC128_HI: written by the preceding op 8/10 */
     } else {  /* 6/7: MIN/MAX f64 via the monotone encoding */
       unsigned long long e = encode_f64(cols.p[j][i]);
       if (op == 6) atomicMin(&acc[j], e); else atomicMax(&acc[j], e);
@@ -3061,7 +3082,14 @@ DEV void aggm_merge_acc(unsigned long long* dst, int op, unsigned long long v) {
     atomicAdd((double*)dst, __longlong_as_double((long long)v));
   else if (op == 4 || op == 6) atomicMin(dst, v);
   else if (op == 5 || op == 7) atomicMax(dst, v);
-  else atomicAdd(dst, v);  /* COUNT + SUM_I64 */
+  else if (op == 8 || op == 10) {
+    /* dec128 lo word: only the carry out of this add goes to dst[1] here;
+     * the sub-table's hi word reaches dst[1] through op 9's own plain add
+     * below when the flush loop gets to j+1 — so hi is added exactly once */
+    unsigned long long old = atomicAdd(dst, v);
+    if ((old + v) < old) atomicAdd(dst + 1, 1ull);
+  }
+  else atomicAdd(dst, v);  /* COUNT + SUM_I64 + DEC128_HI */
 }
 
 template <bool LDS>
@@ -3188,6 +3216,27 @@ __global__ void k_aggm_compact(int64_t cap, const unsigned long long* tab,
   }
 }
 
+/* ops 8/9/10 pairing rule, checked before anything is launched */
+static int agg_dec128_check(const char* who, const gpuq_col* vals,
+                            const int32_t* spec_ops, const int32_t* spec_cols,
+                            int nspecs) {
+  for (int j = 0; j < nspecs; j++) {
+    int op = spec_ops[j];
+    if (op == 8 || op == 10) {
+      if (j + 1 >= nspecs || spec_ops[j + 1] != 9)
+        FAIL(GPUQ_ERR_INVALID, "%s: dec128 op %d at spec %d must be followed by op 9", who, op, j);
+      if (vals[spec_cols[j]].dtype != GPUQ_INT64)
+        FAIL(GPUQ_ERR_INVALID, "%s: dec128 op %d needs an int64 column", who, op);
+      if (op == 10 && vals[spec_cols[j + 1]].dtype != GPUQ_INT64)
+        FAIL(GPUQ_ERR_INVALID, "%s: dec128 partial hi column must be int64", who);
+    } else if (op == 9) {
+      if (j == 0 || (spec_ops[j - 1] != 8 && spec_ops[j - 1] != 10))
+        FAIL(GPUQ_ERR_INVALID, "%s: op 9 at spec %d must follow op 8 or 10", who, j);
+    }
+  }
+  return GPUQ_OK;
+}
+
 extern "C" int gpuq_hash_agg_multi(void* stream, int64_t n, gpuq_col key,
                                    const gpuq_col* vals, const int32_t* spec_ops,
                                    const int32_t* spec_cols, int32_t nspecs,
@@ -3201,6 +3250,7 @@ extern "C" int gpuq_hash_agg_multi(void* stream, int64_t n, gpuq_col key,
   if (nspecs < 1 || nspecs > AGG_MAX_SPECS)
     FAIL(GPUQ_ERR_INVALID, "aggm: nspecs %d not in [1,%d]", nspecs, AGG_MAX_SPECS);
   if (key.dtype != GPUQ_INT64) FAIL(GPUQ_ERR_INVALID, "aggm: key must be int64");
+  if (int rc = agg_dec128_check("aggm", vals, spec_ops, spec_cols, nspecs)) return rc;
   agg_cols cols = {}; agg_ops_spec ops = {}; agg_valid av = {};
   for (int j = 0; j < nspecs; j++) {
     int op = spec_ops[j];
@@ -3215,6 +3265,13 @@ extern "C" int gpuq_hash_agg_multi(void* stream, int64_t n, gpuq_col key,
                               * emit SQL NULL (Sum/Min/Max.scala) */
     } else if (op == 1) {
       av.v[j] = vals[spec_cols[j]].validity;
+    } else if (op == 8 || op == 10) {
+      const gpuq_col& c = vals[spec_cols[j]];
+      cols.p[j] = (const double*)c.data;
+      av.v[j] = c.validity;  /* op 10: the partial's lo-column validity */
+    } else if (op == 9) {
+      /* hi column of a 128-bit partial (op 10); unused after op 8 */
+      if (spec_ops[j - 1] == 10) cols.p[j] = (const double*)vals[spec_cols[j]].data;
     } else if (op != 2) {
       FAIL(GPUQ_ERR_INVALID, "aggm: bad op %d", op);
     }
@@ -3443,6 +3500,7 @@ extern "C" int gpuq_hash_agg_keys(void* stream, int64_t n,
     kc.k[c] = (const int64_t*)key_cols[c].data;
     kc.v[c] = key_cols[c].validity;
   }
+  if (int rc = agg_dec128_check("aggk", vals, spec_ops, spec_cols, nspecs)) return rc;
   agg_cols cols = {}; agg_ops_spec ops = {}; agg_valid av = {};
   for (int j = 0; j < nspecs; j++) {
     int op = spec_ops[j];
@@ -3455,6 +3513,13 @@ extern "C" int gpuq_hash_agg_keys(void* stream, int64_t n,
       av.v[j] = c.validity;
     } else if (op == 1) {
       av.v[j] = vals[spec_cols[j]].validity;
+    } else if (op == 8 || op == 10) {
+      const gpuq_col& c = vals[spec_cols[j]];
+      cols.p[j] = (const double*)c.data;
+      av.v[j] = c.validity;  /* op 10: the partial's lo-column validity */
+    } else if (op == 9) {
+      /* hi column of a 128-bit partial (op 10); unused after op 8 */
+      if (spec_ops[j - 1] == 10) cols.p[j] = (const double*)vals[spec_cols[j]].data;
     } else if (op != 2) {
       FAIL(GPUQ_ERR_INVALID, "aggk: bad op %d", op);
     }
@@ -3720,6 +3785,53 @@ extern "C" int gpuq_nonzero_to_bits(void* stream, int64_t nrows, const int64_t* 
   if (nrows == 0) return GPUQ_OK;
   int64_t nbytes = (nrows + 7) >> 3;
   k_nonzero_to_bits<<<grid1d(nbytes), 256, 0, s>>>(nrows, in, out_bits);
+  HIP_TRY(hipGetLastError());
+  return GPUQ_OK;
+}
+
+/* one thread owns one validity byte (8 rows): no two threads write a byte */
+__global__ void k_dec128_overflow_to_null(int64_t n, const int64_t* lo,
+                                          const int64_t* hi,
+                                          unsigned long long blo,
+                                          unsigned long long bhi, uint8_t* bits) {
+  int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t nbytes = (n + 7) >> 3;
+  int64_t gs = (int64_t)gridDim.x * blockDim.x;
+  for (; b < nbytes; b += gs) {
+    uint8_t keep = 0;
+    int64_t row0 = b << 3;
+    int top = (int)((n - row0) < 8 ? (n - row0) : 8);
+    for (int t = 0; t < top; t++) {
+      unsigned long long l = (unsigned long long)lo[row0 + t];
+      unsigned long long h = (unsigned long long)hi[row0 + t];
+      if ((long long)h < 0) {  /* |x| as u128 (2^127 stays 2^127) */
+        h = ~h + (l == 0);
+        l = ~l + 1;
+      }
+      bool fits = h < bhi || (h == bhi && l < blo);
+      keep |= (uint8_t)((fits ? 1 : 0) << t);
+    }
+    bits[b] &= (uint8_t)(keep | (0xFF << top));
+  }
+}
+
+/* Sum.scala non-ANSI decimal overflow: the 128-bit sum (hi,lo) becomes NULL
+ * when it no longer fits decimal(result_precision, s), i.e. clears validity
+ * bit i unless -10^p < x < 10^p. Bits already clear stay clear. */
+extern "C" int gpuq_dec128_overflow_to_null(void* stream, int64_t nrows,
+                                            const int64_t* lo, const int64_t* hi,
+                                            int32_t result_precision,
+                                            uint8_t* validity_bits) {
+  hipStream_t s = (hipStream_t)stream;
+  if (result_precision < 1 || result_precision > 38)
+    FAIL(GPUQ_ERR_INVALID, "dec128: result precision %d not in [1,38]", result_precision);
+  if (nrows == 0) return GPUQ_OK;
+  unsigned __int128 bound = 1;
+  for (int d = 0; d < result_precision; d++) bound *= 10;
+  int64_t nbytes = (nrows + 7) >> 3;
+  k_dec128_overflow_to_null<<<grid1d(nbytes), 256, 0, s>>>(
+      nrows, lo, hi, (unsigned long long)bound, (unsigned long long)(bound >> 64),
+      validity_bits);
   HIP_TRY(hipGetLastError());
   return GPUQ_OK;
 }

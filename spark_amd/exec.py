@@ -141,10 +141,12 @@ class HashAggregateExec(_CpuNode):
     the UnsafeRow key-tuple case)."""
 
     def __init__(self, group_key, aggs: List[Tuple[str, str]], mode: str, child,
-                 capacity: Optional[int] = None):
+                 capacity: Optional[int] = None,
+                 decimal_precision: Optional[Dict[str, int]] = None):
         super().__init__(child)
         self.group_key, self.aggs, self.mode = group_key, aggs, mode
         self.capacity = capacity
+        self.decimal_precision = decimal_precision
 
     @property
     def group_keys(self):
@@ -152,7 +154,13 @@ class HashAggregateExec(_CpuNode):
 
     @property
     def output(self):
-        return list(self.group_keys) + [f"{fn}({col})" for fn, col in self.aggs]
+        out = list(self.group_keys)
+        for fn, col in self.aggs:
+            if fn == "sum_decimal":   # 128-bit result as (lo, hi) int64 words
+                out += [f"sum_decimal_lo({col})", f"sum_decimal_hi({col})"]
+            else:
+                out.append(f"{fn}({col})")
+        return out
 
 
 class ShuffledHashJoinExec(_CpuNode):
@@ -481,19 +489,32 @@ class GpuHashAggregateExec(SparkPlan):
     partial MIN/MAX merge with MIN/MAX over non-NULL partials. A result is
     NULL iff the merged count of non-null inputs is 0.
 
+    "sum_decimal" is the exact SUM over a decimal(p <= 18, s) column carried
+    as scaled int64 (Sum.scala's Decimal path; "sum" on the same column
+    keeps the wrapping LongType result). Its buffer is a 128-bit (lo, hi)
+    word pair plus a count — dsum_lo(c), dsum_hi(c), count(c) — merged in
+    final mode as a 128-bit add. Final/complete output is two int64 columns
+    sum_decimal_lo(c), sum_decimal_hi(c) sharing one validity bitmap: valid
+    iff count(c) > 0 and |sum| < 10^min(38, p+10) (non-ANSI overflow is
+    NULL). decimal_precision maps column -> input precision p (default 18).
+
     group_key: one name or a tuple (composite GROUP BY via
     gpuq_hash_agg_keys; the reference's UnsafeRow key-tuple path,
     UnsafeFixedWidthAggregationMap.java:39)."""
 
     def __init__(self, group_key, aggs: List[Tuple[str, str]], mode: str,
-                 child, capacity: Optional[int] = None):
+                 child, capacity: Optional[int] = None,
+                 decimal_precision: Optional[Dict[str, int]] = None):
         super().__init__(child)
         assert mode in ("partial", "final", "complete")
         self.group_key, self.aggs, self.mode = group_key, aggs, mode
         self.capacity = capacity
+        self.decimal_precision = decimal_precision
         fns = {fn for fn, _ in self.aggs}
-        assert fns <= {"sum", "count", "count*", "avg", "min", "max"}, \
-            f"unsupported aggs {fns}"
+        assert fns <= {"sum", "count", "count*", "avg", "min", "max",
+                       "sum_decimal"}, f"unsupported aggs {fns}"
+        for c, p in (decimal_precision or {}).items():
+            assert 1 <= p <= 18, f"decimal precision {p} of {c} not in [1,18]"
 
     @property
     def group_keys(self):
@@ -505,8 +526,21 @@ class GpuHashAggregateExec(SparkPlan):
     def agg_out_name(fn: str, col) -> str:
         return "count(1)" if fn == "count*" else f"{fn}({col})"
 
+    @classmethod
+    def _out_names(cls, fn: str, col) -> List[str]:
+        """final/complete output columns of one aggregate."""
+        if fn == "sum_decimal":
+            return [f"sum_decimal_lo({col})", f"sum_decimal_hi({col})"]
+        return [cls.agg_out_name(fn, col)]
+
+    def _result_precision(self, col: str) -> int:
+        # Sum.scala resultType: decimal(min(38, p + 10), s)
+        return min(38, (self.decimal_precision or {}).get(col, 18) + 10)
+
     def _buffer_cols(self, fn: str, col: str) -> List[str]:
         """agg buffer column names (partial-mode output schema)."""
+        if fn == "sum_decimal":
+            return [f"dsum_lo({col})", f"dsum_hi({col})", f"count({col})"]
         if fn == "sum":
             return [f"sum({col})", f"count({col})"]
         if fn == "count":
@@ -527,7 +561,8 @@ class GpuHashAggregateExec(SparkPlan):
                     if b not in seen:
                         seen.add(b); bufs.append(b)
             return keys + bufs
-        return keys + [self.agg_out_name(fn, col) for fn, col in self.aggs]
+        return keys + [n for fn, col in self.aggs
+                       for n in self._out_names(fn, col)]
 
     @property
     def supports_columnar(self):
@@ -552,13 +587,16 @@ class GpuHashAggregateExec(SparkPlan):
 
     def _input_specs(self, batch):
         """specs over RAW input rows (partial/complete) + per-buffer slots.
-        Returns (specs, buffer_slot: name -> spec index)."""
+        Returns (specs, buffer_slot: name -> accumulator word index; a
+        128-bit spec owns two adjacent words)."""
         from . import gpuq
         specs, slot = [], {}
 
-        def add(name, spec):
+        def add(name, spec, hi_name=None):
             if name not in slot:
-                slot[name] = len(specs)
+                slot[name] = self._nwords(specs)
+                if hi_name is not None:
+                    slot[hi_name] = slot[name] + 1
                 specs.append(spec)
 
         for fn, col in self.aggs:
@@ -572,6 +610,11 @@ class GpuHashAggregateExec(SparkPlan):
                 add(f"avg_sum({col})", ("sum", ts, v))
                 add(f"count({col})", ("count", t, v))
             elif fn == "count":
+                add(f"count({col})", ("count", t, v))
+            elif fn == "sum_decimal":
+                # the count companion is unconditional: the buffer layout
+                # must not depend on a batch's validity or on the mode
+                add(f"dsum_lo({col})", ("sum_dec128", t, v), f"dsum_hi({col})")
                 add(f"count({col})", ("count", t, v))
             else:
                 add(f"{fn}({col})", (fn, t, v))
@@ -591,17 +634,25 @@ class GpuHashAggregateExec(SparkPlan):
         for sums/counts, MIN/MAX over non-NULL partials."""
         specs, slot = [], {}
 
-        def add(name, kind):
+        def add(name, kind, hi_name=None):
             if name in slot:
                 return
             t = batch.column(name)
             v = batch.validity(name)
-            slot[name] = len(specs)
-            specs.append((kind, t, v))
+            slot[name] = self._nwords(specs)
+            if hi_name is None:
+                specs.append((kind, t, v))
+            else:
+                slot[hi_name] = slot[name] + 1
+                specs.append((kind, t, v, batch.column(hi_name)))
 
         for fn, col in self.aggs:
             for b in self._buffer_cols(fn, col):
-                if b.startswith("count"):
+                if b.startswith("dsum_lo"):
+                    add(b, "merge_dec128", f"dsum_hi({col})")
+                elif b.startswith("dsum_hi"):
+                    pass              # the hi word of the pair above
+                elif b.startswith("count"):
                     add(b, "sum")     # SUM_I64: exact merged counts
                 elif b.startswith("min"):
                     add(b, "min")
@@ -614,6 +665,12 @@ class GpuHashAggregateExec(SparkPlan):
             specs.append(("count*",))
         return specs, slot
 
+    @staticmethod
+    def _nwords(specs) -> int:
+        """accumulator words (= kernel specs) a spec list expands to."""
+        return sum(2 if s[0] in ("sum_dec128", "merge_dec128") else 1
+                   for s in specs)
+
     def _agg_batches(self, batches):
         from . import gpuq
         keys = self.group_keys
@@ -625,7 +682,7 @@ class GpuHashAggregateExec(SparkPlan):
             per_specs = [self._input_specs(b) for b in batches]
         slot = per_specs[0][1]
         mg = min(total, cap) + 2
-        nspecs = len(per_specs[0][0])
+        nspecs = self._nwords(per_specs[0][0])
         last_i = len(batches) - 1
         if len(keys) == 0:
             # global aggregate (empty grouping): one output row even on
@@ -643,11 +700,15 @@ class GpuHashAggregateExec(SparkPlan):
                     except KeyError:
                         return torch.float64
                 names = (list(slot) if self.mode == "partial"
-                         else [self.agg_out_name(fn, col)
-                               for fn, col in self.aggs])
+                         else [n for fn, col in self.aggs
+                               for n in self._out_names(fn, col)])
                 for name in names:
                     if name.startswith("count"):
                         cols[name] = torch.zeros(1, dtype=torch.int64, device=dev)
+                    elif name.startswith(("dsum_", "sum_decimal_")):
+                        cols[name] = torch.zeros(1, dtype=torch.int64, device=dev)
+                        validity[name] = torch.zeros(1, dtype=torch.uint8,
+                                                     device=dev)
                     elif name.startswith(("min(", "max(", "sum(")):
                         cols[name] = torch.zeros(1, dtype=src_dtype(name),
                                                  device=dev)
@@ -765,6 +826,18 @@ class GpuHashAggregateExec(SparkPlan):
                     cols[out] = accs[slot[f"count({col})"]]
                     continue
                 cnt_slot = slot.get(f"count({col})")
+                if fn == "sum_decimal":
+                    lo = accs[slot[f"dsum_lo({col})"]]
+                    hi = accs[slot[f"dsum_hi({col})"]]
+                    # NULL iff no non-null input OR the sum no longer fits
+                    # decimal(min(38, p+10), s) (Sum.scala, non-ANSI)
+                    bits = gpuq.dec128_overflow_to_null(
+                        lo, hi, self._result_precision(col),
+                        gpuq.nonzero_to_bits(accs[cnt_slot]))
+                    for n_, t_ in zip(self._out_names(fn, col), (lo, hi)):
+                        cols[n_] = t_
+                        validity[n_] = bits
+                    continue
                 if fn == "avg":
                     # Average.evaluateExpression: sum / cast(count)
                     cols[out] = gpuq.project_binop(
@@ -1169,8 +1242,10 @@ class GpuColumnarRule:
         if isinstance(plan, SortExec):
             return GpuSortExec(plan.sort_order, plan.global_sort, *children)
         if isinstance(plan, HashAggregateExec):
-            return GpuHashAggregateExec(plan.group_key, plan.aggs, plan.mode,
-                                        *children, capacity=plan.capacity)
+            return GpuHashAggregateExec(
+                plan.group_key, plan.aggs, plan.mode, *children,
+                capacity=plan.capacity,
+                decimal_precision=plan.decimal_precision)
         if isinstance(plan, ShuffledHashJoinExec):
             return GpuShuffledHashJoinExec(plan.left_key, plan.right_key,
                                            plan.build_side, *children,

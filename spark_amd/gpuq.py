@@ -108,6 +108,8 @@ def lib() -> ctypes.CDLL:
         L.gpuq_u8_to_bits.argtypes = [vp, i64, vp, vp]
         L.gpuq_nonzero_to_bits.restype = i32
         L.gpuq_nonzero_to_bits.argtypes = [vp, i64, vp, vp]
+        L.gpuq_dec128_overflow_to_null.restype = i32
+        L.gpuq_dec128_overflow_to_null.argtypes = [vp, i64, vp, vp, i32, vp]
         L.gpuq_maskbit_to_bits.restype = i32
         L.gpuq_maskbit_to_bits.argtypes = [vp, i64, vp, i32, vp]
         L.gpuq_minmax_i64.restype = i32
@@ -438,12 +440,31 @@ def _build_agg_specs(specs, dev, mg, placeholder):
     """specs: list of (kind, col_tensor_or_None[, validity]) with kind in
     {"sum","count","count*","min","max"}. Op codes per gpuq.h:
     0=SUM_F64 1=COUNT(col) 2=COUNT(*) 3=SUM_I64 4=MIN_I64 5=MAX_I64
-    6=MIN_F64 7=MAX_F64. Returns (cols_arr, ops_arr, cid_arr, outs)."""
+    6=MIN_F64 7=MAX_F64. Two kinds take a 128-bit (lo, hi) accumulator and
+    expand to an op PAIR with TWO entries in outs (so indices into outs stay
+    one per accumulator word; at most 12 words per call):
+    ("sum_dec128", t, v) -> ops 8,9 over an int64 scaled-decimal column;
+    ("merge_dec128", t_lo, v, t_hi) -> ops 10,9 over 128-bit partials.
+    Returns (cols_arr, ops_arr, cid_arr, outs)."""
     cols, ops, colidx, outs = [], [], [], []
     for s in specs:
         kind = s[0]
         t = s[1] if len(s) > 1 else None
         v = s[2] if len(s) > 2 else None
+        if kind in ("sum_dec128", "merge_dec128"):
+            if t.dtype != torch.int64:
+                raise ValueError(f"{kind} needs an int64 column")
+            ops += [8 if kind == "sum_dec128" else 10, 9]
+            colidx += [len(cols), len(cols)]
+            cols.append(_col(t, v))
+            if kind == "merge_dec128":
+                if s[3].dtype != torch.int64:
+                    raise ValueError("merge_dec128 needs an int64 hi column")
+                colidx[-1] = len(cols)
+                cols.append(_col(s[3]))
+            outs += [torch.empty(mg, dtype=torch.int64, device=dev)
+                     for _ in range(2)]
+            continue
         if kind == "count*":
             ops.append(2); colidx.append(0)
             outs.append(torch.empty(mg, dtype=torch.int64, device=dev))
@@ -464,7 +485,7 @@ def _build_agg_specs(specs, dev, mg, placeholder):
         cols.append(_col(t, v))
     if not cols:
         cols = [_col(placeholder)]  # placeholder, unused
-    nspecs = len(specs)
+    nspecs = len(ops)
     cols_arr = (_Col * len(cols))(*cols)
     ops_arr = (ctypes.c_int32 * nspecs)(*ops)
     cid_arr = (ctypes.c_int32 * nspecs)(*colidx)
@@ -486,9 +507,9 @@ def hash_agg_multi(keys: torch.Tensor, specs, capacity: int, key_validity=None,
     [acc_j...]) sliced to ngroups, or None before finalize."""
     n = keys.numel()
     dev = keys.device
-    nspecs = len(specs)
     mg = max_groups or capacity + 2
     cols_arr, ops_arr, cid_arr, outs = _build_agg_specs(specs, dev, mg, keys)
+    nspecs = len(outs)  # accumulator words (a dec128 spec is two)
     outp_arr = (ctypes.c_void_p * nspecs)(*[t.data_ptr() for t in outs])
     if workspace is None:
         workspace = agg_multi_workspace(capacity, nspecs, dev)
@@ -517,9 +538,9 @@ def hash_agg_keys(key_cols, specs, capacity: int, key_validities=None,
     n = key_cols[0].numel()
     dev = key_cols[0].device
     kv = key_validities or [None] * nkeys
-    nspecs = len(specs)
     mg = max_groups or capacity + 2
     cols_arr, ops_arr, cid_arr, outs = _build_agg_specs(specs, dev, mg, key_cols[0])
+    nspecs = len(outs)
     outp_arr = (ctypes.c_void_p * nspecs)(*[t.data_ptr() for t in outs])
     keys_arr = (_Col * nkeys)(*[_col(k, v) for k, v in zip(key_cols, kv)])
     okeys = [torch.empty(mg, dtype=torch.int64, device=dev) for _ in range(nkeys)]
@@ -592,6 +613,29 @@ def nonzero_to_bits(col: torch.Tensor) -> torch.Tensor:
     out = torch.empty(_bitmap_bytes(n), dtype=torch.uint8, device=col.device)
     _check(lib().gpuq_nonzero_to_bits(_stream(), n, col.data_ptr(), out.data_ptr()))
     return out
+
+
+def dec128_overflow_to_null(lo: torch.Tensor, hi: torch.Tensor,
+                            result_precision: int, validity_bits=None):
+    """Clear validity bit i where |(hi[i], lo[i])| >= 10**result_precision
+    (Sum.scala: non-ANSI decimal overflow evaluates to NULL). Updates
+    validity_bits in place (all-valid when None) and returns it."""
+    n = lo.numel()
+    if validity_bits is None:
+        validity_bits = torch.full((_bitmap_bytes(n),), 0xFF, dtype=torch.uint8,
+                                   device=lo.device)
+    _check(lib().gpuq_dec128_overflow_to_null(
+        _stream(), n, lo.data_ptr(), hi.data_ptr(), result_precision,
+        validity_bits.data_ptr()))
+    return validity_bits
+
+
+def dec128_to_pyints(lo: torch.Tensor, hi: torch.Tensor):
+    """(lo, hi) int64 word columns -> list of Python ints,
+    (hi << 64) | (lo & (2**64-1)). Host-side helper (copies to the CPU)."""
+    m = (1 << 64) - 1
+    return [(h << 64) | (l & m)
+            for l, h in zip(lo.cpu().tolist(), hi.cpu().tolist())]
 
 
 def maskbit_to_bits(mask: torch.Tensor, bit: int) -> torch.Tensor:
