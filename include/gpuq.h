@@ -337,6 +337,14 @@ int gpuq_join_probe_i64(void* stream, int64_t probe_rows, gpuq_col probe_key,
 /* input order. Project: elementwise a OP b (column or literal).     */
 /* ---------------------------------------------------------------- */
 
+/* Comparison rules (Spark, non-ANSI):
+ *  - a NULL input row never passes, GPUQ_CMP_NE included;
+ *  - float64 uses Spark's total order (SQLOrderingUtil.compareDoubles), the
+ *    one the sort and MIN/MAX already follow: -0.0 == 0.0, NaN == NaN, and
+ *    NaN is greater than every other value, +inf included. So `x > 0.5` and
+ *    `x >= 0.5` keep NaN rows, and a NaN literal is legal: `x == NaN` keeps
+ *    exactly the NaN rows, `x < NaN` every other valid row;
+ *  - int64 compares exactly against lit_i64 (lit_f64 is ignored). */
 #define GPUQ_CMP_EQ 0
 #define GPUQ_CMP_LT 1
 #define GPUQ_CMP_LE 2
@@ -356,9 +364,28 @@ int gpuq_filter_cmp(void* stream, int64_t nrows, gpuq_col col, int32_t op,
 #define GPUQ_BINOP_DIV 3
 #define GPUQ_BINOP_RSUB 4  /* out = b - a (literal - column) */
 
+/* Arithmetic rules (Spark, non-ANSI): int64 + - * wrap modulo 2^64; int64 /
+ * truncates toward zero and INT64_MIN / -1 == INT64_MIN (Java long); float64
+ * is the IEEE result of the single operation.
+ *
+ * gpuq_project_binop tracks no NULLs: a.validity must be NULL, the caller
+ * owns validity (AVG = sum / count derives it from the count) and an
+ * integral zero divisor yields 0. b is read with a's dtype. */
 int gpuq_project_binop(void* stream, int64_t nrows, gpuq_col a,
                        const void* b /* second column's data or NULL for literal */,
                        double lit_f64, int64_t lit_i64, int32_t op, void* out);
+
+/* NULL-aware projection. b.data == NULL makes b the literal (lit_f64 for a
+ * float64 a, lit_i64 for an int64 a; b.validity must then be NULL); otherwise
+ * b.dtype must equal a.dtype. Output row i is valid iff a and b are valid at
+ * i and the op is not a division by zero: x / 0 is NULL (for float64, 0.0
+ * and -0.0 alike; a NaN divisor is not zero). NULL output rows hold 0.
+ * out_validity_bits: (nrows + 7) / 8 bytes; may be NULL only when nothing
+ * can be NULL (no input bitmap and op != GPUQ_BINOP_DIV). */
+int gpuq_project_binop_nullable(void* stream, int64_t nrows, gpuq_col a,
+                                gpuq_col b, double lit_f64, int64_t lit_i64,
+                                int32_t op, void* out,
+                                uint8_t* out_validity_bits);
 
 /* int64 -> float64 cast (AVG evaluation: sum / cast(count)) */
 int gpuq_cast_i64_f64(void* stream, int64_t nrows, const int64_t* in, double* out);

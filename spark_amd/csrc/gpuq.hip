@@ -3976,7 +3976,23 @@ extern "C" int gpuq_unpack2_i64(void* stream, int64_t nrows, const int64_t* in,
  * (col OP col / col OP literal) on int64/float64.
  */
 
+/* float64 follows Spark's total order (SQLOrderingUtil.compareDoubles), the
+ * same one the sort and MIN/MAX use: NaN == NaN and NaN is greater than every
+ * other value, +inf included; -0.0 == 0.0. Non-NaN operands take the plain
+ * IEEE comparison below. */
 DEV bool filter_cmp_f64(double v, int op, double lit) {
+  if (v != v || lit != lit) {
+    bool vn = v != v, ln = lit != lit;
+    int c = (vn && ln) ? 0 : (vn ? 1 : -1);
+    switch (op) {
+      case 0: return c == 0;
+      case 1: return c < 0;
+      case 2: return c <= 0;
+      case 3: return c > 0;
+      case 4: return c >= 0;
+      default: return c != 0;
+    }
+  }
   switch (op) {
     case 0: return v == lit;
     case 1: return v < lit;
@@ -4069,7 +4085,31 @@ extern "C" int gpuq_filter_cmp(void* stream, int64_t n, gpuq_col col, int32_t op
   return GPUQ_OK;
 }
 
-/* out = a OP b (b = column or broadcast literal) */
+/* One int64 operation with Java long semantics (Spark non-ANSI): + - * wrap
+ * modulo 2^64, done in uint64_t because signed overflow is undefined in C++;
+ * / truncates toward zero and INT64_MIN / -1 == INT64_MIN (divisor -1 is an
+ * unsigned negation; the signed quotient would overflow). The caller rules
+ * out a zero divisor. */
+template <int OP>
+DEV int64_t binop_i64(int64_t x, int64_t y) {
+  uint64_t ux = (uint64_t)x, uy = (uint64_t)y;
+  if (OP == 0) return (int64_t)(ux + uy);
+  if (OP == 1) return (int64_t)(ux - uy);
+  if (OP == 2) return (int64_t)(ux * uy);
+  if (OP == 4) return (int64_t)(uy - ux);
+  if (y == -1) return (int64_t)(0 - ux);
+  return x / y;
+}
+
+template <int OP>
+DEV double binop_f64(double x, double y) {
+  return OP == 0 ? x + y : OP == 1 ? x - y : OP == 2 ? x * y
+         : OP == 4 ? y - x : x / y;
+}
+
+/* out = a OP b (b = column or broadcast literal), no NULL tracking: the
+ * caller owns validity (AVG = sum / count fixes it from the count). An
+ * integral zero divisor yields 0 here. */
 template <int DTYPE, int OP, bool B_IS_LIT>
 __global__ void k_project_binop(int64_t n, const void* a, const void* b,
                                 double lit_f, int64_t lit_i, void* out) {
@@ -4079,16 +4119,54 @@ __global__ void k_project_binop(int64_t n, const void* a, const void* b,
     if (DTYPE == GPUQ_FLOAT64) {
       double x = ((const double*)a)[i];
       double y = B_IS_LIT ? lit_f : ((const double*)b)[i];
-      double r = OP == 0 ? x + y : OP == 1 ? x - y : OP == 2 ? x * y
-                 : OP == 4 ? y - x : x / y;
-      ((double*)out)[i] = r;
+      ((double*)out)[i] = binop_f64<OP>(x, y);
     } else {
       int64_t x = ((const int64_t*)a)[i];
       int64_t y = B_IS_LIT ? lit_i : ((const int64_t*)b)[i];
-      int64_t r = OP == 0 ? x + y : OP == 1 ? x - y : OP == 2 ? x * y
-                  : OP == 4 ? y - x : (y == 0 ? 0 : x / y);
-      ((int64_t*)out)[i] = r;
+      ((int64_t*)out)[i] = (OP == 3 && y == 0) ? 0 : binop_i64<OP>(x, y);
     }
+  }
+}
+
+/* NULL-aware form: the output row is valid iff both inputs are valid and the
+ * op is not a division by zero (Spark non-ANSI Divide: x / 0 is NULL; for
+ * float64 -0.0 is a zero too). NULL output rows hold 0, never the bytes that
+ * sat under an input NULL.
+ * One thread per row, so loads and stores coalesce like the plain kernel's.
+ * A wavefront covers 64 consecutive rows starting at a multiple of 64 (block
+ * and grid stride are multiples of 64), i.e. exactly 8 bitmap bytes: the
+ * lanes' valid bits are collected with one ballot and every 8th lane stores
+ * its byte, so no two threads write the same byte and no atomics are needed.
+ * The loop bound is wave-uniform (all 64 lanes reach the ballot); lanes past
+ * n vote 0, which also zeroes the spare bits of the last byte. */
+template <int DTYPE, int OP, bool B_IS_LIT>
+__global__ void k_project_binop_nullable(int64_t n, const void* a,
+                                         const uint8_t* a_valid, const void* b,
+                                         const uint8_t* b_valid, double lit_f,
+                                         int64_t lit_i, void* out,
+                                         uint8_t* out_bits) {
+  int lane = threadIdx.x & 63;
+  int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane);
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; base < n; base += stride) {
+    int64_t i = base + lane;
+    bool ok = i < n;
+    if (ok) {
+      ok = bit_valid(a_valid, i) && (B_IS_LIT || bit_valid(b_valid, i));
+      if (DTYPE == GPUQ_FLOAT64) {
+        double x = ((const double*)a)[i];
+        double y = B_IS_LIT ? lit_f : ((const double*)b)[i];
+        if (OP == 3 && y == 0.0) ok = false;
+        ((double*)out)[i] = ok ? binop_f64<OP>(x, y) : 0.0;
+      } else {
+        int64_t x = ((const int64_t*)a)[i];
+        int64_t y = B_IS_LIT ? lit_i : ((const int64_t*)b)[i];
+        if (OP == 3 && y == 0) ok = false;
+        ((int64_t*)out)[i] = ok ? binop_i64<OP>(x, y) : 0;
+      }
+    }
+    uint64_t m = __ballot(ok);
+    if ((lane & 7) == 0 && i < n) out_bits[i >> 3] = (uint8_t)(m >> lane);
   }
 }
 
@@ -4098,7 +4176,8 @@ extern "C" int gpuq_project_binop(void* stream, int64_t n, gpuq_col a,
                                   void* out) {
   hipStream_t s = (hipStream_t)stream;
   if (op < 0 || op > 4) FAIL(GPUQ_ERR_INVALID, "project: bad op %d", op);
-  if (a.validity) FAIL(GPUQ_ERR_INVALID, "project: validity not yet supported");
+  if (a.validity)
+    FAIL(GPUQ_ERR_INVALID, "project: validity needs gpuq_project_binop_nullable");
   dim3 g = grid1d(n);
 #define PJ(DT, OPV) do { \
     if (b) k_project_binop<DT, OPV, false><<<g, 256, 0, s>>>(n, a.data, b, lit_f, lit_i, out); \
@@ -4116,6 +4195,48 @@ extern "C" int gpuq_project_binop(void* stream, int64_t n, gpuq_col a,
     FAIL(GPUQ_ERR_INVALID, "project: unsupported dtype %d", a.dtype);
   }
 #undef PJ
+  HIP_TRY(hipGetLastError());
+  return GPUQ_OK;
+}
+
+extern "C" int gpuq_project_binop_nullable(void* stream, int64_t n, gpuq_col a,
+                                           gpuq_col b /* data NULL => literal */,
+                                           double lit_f, int64_t lit_i,
+                                           int32_t op, void* out,
+                                           uint8_t* out_bits) {
+  hipStream_t s = (hipStream_t)stream;
+  if (op < 0 || op > 4) FAIL(GPUQ_ERR_INVALID, "project: bad op %d", op);
+  if (a.dtype != GPUQ_FLOAT64 && a.dtype != GPUQ_INT64)
+    FAIL(GPUQ_ERR_INVALID, "project: unsupported dtype %d", a.dtype);
+  if (b.data && b.dtype != a.dtype)
+    FAIL(GPUQ_ERR_INVALID, "project: operand dtypes differ (%d vs %d)",
+         a.dtype, b.dtype);
+  if (!b.data && b.validity)
+    FAIL(GPUQ_ERR_INVALID, "project: a literal operand has no validity");
+  if (n == 0) return GPUQ_OK;   /* an empty bitmap's pointer may be NULL */
+  if (!out_bits) {
+    /* nothing can be NULL: the plain kernel */
+    if (a.validity || b.validity || op == GPUQ_BINOP_DIV)
+      FAIL(GPUQ_ERR_INVALID,
+           "project: nullable inputs and '/' need an output bitmap");
+    return gpuq_project_binop(stream, n, a, b.data, lit_f, lit_i, op, out);
+  }
+  dim3 g = grid1d(n);   /* 256-thread blocks: whole wavefronts */
+#define PJN(DT, OPV) do { \
+    if (b.data) k_project_binop_nullable<DT, OPV, false><<<g, 256, 0, s>>>( \
+        n, a.data, a.validity, b.data, b.validity, lit_f, lit_i, out, out_bits); \
+    else k_project_binop_nullable<DT, OPV, true><<<g, 256, 0, s>>>( \
+        n, a.data, a.validity, b.data, b.validity, lit_f, lit_i, out, out_bits); \
+  } while (0)
+#define PJN_OPS(DT) do { \
+    if (op == 0) PJN(DT, 0); else if (op == 1) PJN(DT, 1); \
+    else if (op == 2) PJN(DT, 2); else if (op == 4) PJN(DT, 4); \
+    else PJN(DT, 3); \
+  } while (0)
+  if (a.dtype == GPUQ_FLOAT64) PJN_OPS(GPUQ_FLOAT64);
+  else PJN_OPS(GPUQ_INT64);
+#undef PJN_OPS
+#undef PJN
   HIP_TRY(hipGetLastError());
   return GPUQ_OK;
 }
@@ -4139,7 +4260,9 @@ extern "C" int gpuq_cast_i64_f64(void* stream, int64_t n, const int64_t* in,
 __global__ void k_range_i64(int64_t n, int64_t start, int64_t step, int64_t* out) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) out[i] = start + i * step;
+  /* wraps like Java long arithmetic (unsigned: no signed-overflow UB) */
+  for (; i < n; i += stride)
+    out[i] = (int64_t)((uint64_t)start + (uint64_t)i * (uint64_t)step);
 }
 
 extern "C" int gpuq_range_i64(void* stream, int64_t n, int64_t start,

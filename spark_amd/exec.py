@@ -1147,7 +1147,10 @@ class GpuFilterExec(SparkPlan):
 
 class GpuProjectExec(SparkPlan):
     """Replaces ProjectExec for elementwise binary
-    arithmetic; pass-through entries keep their column."""
+    arithmetic; pass-through entries keep their column and its validity
+    bitmap. A computed row is NULL iff an input row is NULL or the op is a
+    division by zero (Spark non-ANSI); its column carries a bitmap unless
+    nothing can be NULL (no input bitmap and op is not `/`)."""
 
     def __init__(self, projections, child):
         super().__init__(child)
@@ -1164,18 +1167,23 @@ class GpuProjectExec(SparkPlan):
     def execute_columnar(self):
         from . import gpuq
         for batch in self.children[0].execute_columnar():
-            cols = {}
+            cols, validity = {}, {}
             for p in self.projections:
                 if isinstance(p, str):
                     cols[p] = batch.column(p)
+                    v = batch.validity(p)
                 else:
                     out_name, a, op, b, lit = p
-                    cols[out_name] = gpuq.project_binop(
+                    p = out_name
+                    cols[p], v = gpuq.project_binop_nullable(
                         batch.column(a), op,
                         b=batch.column(b) if b is not None else None,
-                        literal=lit)
+                        literal=lit, a_validity=batch.validity(a),
+                        b_validity=batch.validity(b) if b is not None else None)
+                if v is not None:
+                    validity[p] = v
             batch.close()
-            yield ColumnarBatch(cols)
+            yield ColumnarBatch(cols, validity=validity or None)
 
 
 class GpuBroadcastExchangeExec(SparkPlan):

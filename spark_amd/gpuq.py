@@ -144,6 +144,10 @@ def lib() -> ctypes.CDLL:
         L.gpuq_project_binop.restype = i32
         L.gpuq_project_binop.argtypes = [vp, i64, _Col, vp, ctypes.c_double, i64,
                                          i32, vp]
+        L.gpuq_project_binop_nullable.restype = i32
+        L.gpuq_project_binop_nullable.argtypes = [vp, i64, _Col, _Col,
+                                                  ctypes.c_double, i64, i32,
+                                                  vp, vp]
         L.gpuq_range_i64.restype = i32
         L.gpuq_range_i64.argtypes = [vp, i64, i64, i64, vp]
         L.gpuq_cast_i64_f64.restype = i32
@@ -367,61 +371,127 @@ def filter_cmp(col: torch.Tensor, op: str, literal, workspace=None, validity=Non
     """Stable filter: returns (perm[:count], count) — passing rows in input
     order (FilterExec replacement for col OP literal predicates).
 
-    An int64 column compared against a fractional literal follows Spark's
+    A NULL row never passes. float64 columns follow Spark's ordering
+    (NaN == NaN, NaN greater than everything, -0.0 == 0.0); inf and NaN
+    literals are passed through to the kernel.
+
+    An int64 column compared against a float literal follows Spark's
     cast-to-double comparison semantics: the predicate is rewritten to an
     equivalent integer comparison (e.g. k < 0.5 == k <= 0), never truncated
-    (k < 0.5 must keep k == 0)."""
+    (k < 0.5 must keep k == 0). +/-inf and NaN literals become constant
+    predicates (NaN is greater than every double a bigint casts to)."""
     n = col.numel()
     dev = col.device
     import math
     I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
-    if col.dtype == torch.int64 and isinstance(literal, float) \
-            and math.isinf(literal):
-        # +/-inf literal: constant predicate
-        all_ops = ("<", "<=") if literal > 0 else (">", ">=")
-        literal, op = I64_MIN, (">=" if op in all_ops or op == "!=" else "<")
-    if col.dtype == torch.int64 and isinstance(literal, float) \
-            and math.isfinite(literal) \
-            and (literal != int(literal)
-                 or not (I64_MIN <= int(literal) <= I64_MAX)):
-        f = math.floor(literal)
-        if op in ("==",):
-            op, literal = "<", I64_MIN          # never true
-        elif op in ("!=",):
-            op, literal = ">=", I64_MIN         # true for every valid row
-        elif op in ("<", "<="):
-            # col < L  <=>  col <= floor(L)
-            op, literal = ("<=", f) if f >= I64_MIN else ("<", I64_MIN)
-            if f > I64_MAX:
-                op, literal = ">=", I64_MIN     # all pass
-        else:  # > / >=  : col > L <=> col >= floor(L)+1
-            g = f + 1
-            op, literal = (">=", g) if g <= I64_MAX else ("<", I64_MIN)
-            if g < I64_MIN:
-                op, literal = ">=", I64_MIN     # all pass
+    ALL, NONE = (">=", I64_MIN), ("<", I64_MIN)   # every valid row / no row
+    if col.dtype == torch.int64 and isinstance(literal, float):
+        if math.isnan(literal):
+            op, literal = ALL if op in ("<", "<=", "!=") else NONE
+        elif math.isinf(literal):
+            all_ops = ("<", "<=") if literal > 0 else (">", ">=")
+            op, literal = ALL if op in all_ops or op == "!=" else NONE
+        elif literal != int(literal) \
+                or not (I64_MIN <= int(literal) <= I64_MAX):
+            f = math.floor(literal)
+            if op in ("==",):
+                op, literal = NONE
+            elif op in ("!=",):
+                op, literal = ALL
+            elif op in ("<", "<="):
+                # col < L  <=>  col <= floor(L)
+                op, literal = ("<=", f) if f >= I64_MIN else NONE
+                if f > I64_MAX:
+                    op, literal = ALL
+            else:  # > / >=  : col > L <=> col >= floor(L)+1
+                g = f + 1
+                op, literal = (">=", g) if g <= I64_MAX else NONE
+                if g < I64_MIN:
+                    op, literal = ALL
+    if col.dtype == torch.int64:
+        lit_i = int(literal)
+        lit_f = float(lit_i)
+    else:
+        lit_f = float(literal)   # inf / NaN included; the kernel orders them
+        lit_i = 0
     if workspace is None:
         workspace = torch.empty(lib().gpuq_filter_workspace_bytes(n),
                                 dtype=torch.uint8, device=dev)
     perm = torch.empty(n, dtype=torch.int32, device=dev)
     cnt = torch.zeros(1, dtype=torch.int64, device=dev)
     _check(lib().gpuq_filter_cmp(_stream(), n, _col(col, validity), CMP[op],
-                                 float(literal), int(literal),
+                                 lit_f, lit_i,
                                  perm.data_ptr(), cnt.data_ptr(),
                                  workspace.data_ptr(), workspace.numel()))
     c = int(cnt.item())
     return perm[:c], c
 
 
+def _binop_operands(a: torch.Tensor, b, literal):
+    """(lit_f64, lit_i64) for a OP b after the operand type checks: a column
+    b must have a's dtype, and an int64 column takes only integral literals
+    (nothing is truncated or reinterpreted silently)."""
+    if a.dtype not in (torch.int64, torch.float64):
+        raise ValueError(f"project_binop: unsupported dtype {a.dtype}")
+    if b is not None:
+        if literal is not None:
+            raise ValueError("project_binop: give b or literal, not both")
+        if b.dtype != a.dtype:
+            raise ValueError(f"project_binop: operand dtypes differ "
+                             f"({a.dtype} vs {b.dtype})")
+        if b.numel() != a.numel():
+            raise ValueError("project_binop: operand lengths differ")
+        return 0.0, 0
+    if literal is None:
+        raise ValueError("project_binop: needs b or literal")
+    if a.dtype == torch.float64:
+        return float(literal), 0
+    import math
+    if isinstance(literal, float) and (not math.isfinite(literal)
+                                       or literal != int(literal)):
+        raise ValueError(f"project_binop: non-integral literal {literal!r} "
+                         f"on an int64 column")
+    lit_i = int(literal)
+    if not -(1 << 63) <= lit_i < (1 << 63):
+        raise ValueError(f"project_binop: literal {literal!r} exceeds int64")
+    return float(lit_i), lit_i
+
+
 def project_binop(a: torch.Tensor, op: str, b=None, literal=None):
-    """Elementwise a OP b (b: tensor or None with literal)."""
+    """Elementwise a OP b (b: tensor or None with literal), no NULL tracking:
+    the caller owns validity (AVG = sum / count derives it from the count).
+    Projections over nullable inputs and any `/` whose zero divisors must
+    come out NULL go through project_binop_nullable."""
     n = a.numel()
+    lit_f, lit_i = _binop_operands(a, b, literal)
     out = torch.empty(n, dtype=a.dtype, device=a.device)
-    lit_f = float(literal) if literal is not None else 0.0
-    lit_i = int(literal) if literal is not None else 0
     _check(lib().gpuq_project_binop(_stream(), n, _col(a),
                                     b.data_ptr() if b is not None else None,
                                     lit_f, lit_i, BINOP[op], out.data_ptr()))
     return out
+
+
+def project_binop_nullable(a: torch.Tensor, op: str, b=None, literal=None,
+                           a_validity=None, b_validity=None):
+    """NULL-aware a OP b -> (out, validity bitmap or None). A row is valid
+    iff both inputs are valid and the op is not a division by zero (Spark
+    non-ANSI: x / 0 is NULL; for float64 -0.0 is zero too). NULL rows hold 0.
+    The bitmap is omitted only when nothing can be NULL: no input bitmap and
+    op is not `/`."""
+    n = a.numel()
+    lit_f, lit_i = _binop_operands(a, b, literal)
+    if b is None and b_validity is not None:
+        raise ValueError("project_binop: a literal operand has no validity")
+    out = torch.empty(n, dtype=a.dtype, device=a.device)
+    bits = None
+    if a_validity is not None or b_validity is not None or op == "/":
+        bits = torch.empty(_bitmap_bytes(n), dtype=torch.uint8, device=a.device)
+    bcol = _col(b, b_validity) if b is not None \
+        else _Col(None, None, _DTYPE_MAP[a.dtype])
+    _check(lib().gpuq_project_binop_nullable(
+        _stream(), n, _col(a, a_validity), bcol, lit_f, lit_i, BINOP[op],
+        out.data_ptr(), _dp(bits)))
+    return out, bits
 
 
 def cast_i64_f64(t: torch.Tensor) -> torch.Tensor:

@@ -1,11 +1,15 @@
 """Randomized GPU-vs-oracle parity fuzz: random shapes, ranges, descs,
-validity patterns across sort/partition/agg/join. Seeded per iteration and
+validity patterns across sort/partition/agg/join and the filter/project
+kernels (the latter against tests/expr_ref.py). Seeded per iteration and
 bounded by FUZZ_SECONDS (default 240)."""
 import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _ROOT)
+sys.path.insert(0, os.path.join(_ROOT, "tests"))
 import numpy as np
 import torch
 import oracle
+import expr_ref
 from spark_amd import gpuq as gq
 
 BUDGET = float(os.environ.get("FUZZ_SECONDS", 240))
@@ -17,15 +21,116 @@ fails = 0
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
+# filter/project sizes: the bitmap-byte, block, compaction-tile and grid-cap
+# boundaries, or a random n <= 200 000 (the reference is row-by-row Python)
+EXPR_SIZES = [0, 1, 7, 8, 9, 255, 256, 257, 5631, 5632, 5633, 11265,
+              524288 + 257]
+I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
+
+def expr_n():
+    if rng.integers(2):
+        return int(rng.choice(EXPR_SIZES))
+    return int(rng.integers(0, 200_001))
+
+def expr_valid(n):
+    """None, or a bool mask with a random NULL density"""
+    if rng.integers(3) == 0:
+        return None, None
+    valid = rng.random(n) >= rng.random()
+    return valid, torch.from_numpy(np.packbits(valid, bitorder="little")).cuda()
+
+def unpack(bits, n):
+    return np.unpackbits(bits.cpu().numpy(), bitorder="little")[:n].astype(bool)
+
+def same_values(got, exp, valid):
+    g, e = got[valid], exp[valid]
+    if got.dtype == np.float64:
+        return bool(((g.view(np.uint64) == e.view(np.uint64))
+                     | (np.isnan(g) & np.isnan(e))).all())
+    return bool((g == e).all())
+
 while time.time() < t_end:
     it += 1
     op = rng.choice(["sort_i64", "sort_f64", "sort_nulls", "partition",
                      "agg", "join", "minmax_agg", "composite_agg",
-                     "typed_join", "partition_multi"])
+                     "typed_join", "partition_multi",
+                     "filter_i64", "filter_f64", "project"])
     n = int(rng.integers(1, 3_000_000))
     seed = int(rng.integers(0, 2**31))
     try:
-        if op == "sort_i64":
+        if op == "filter_i64":
+            n = expr_n()
+            r = int(rng.choice([3, 7, 1000]))
+            vals = rng.integers(-r, r + 1, size=n, dtype=np.int64)
+            if n and rng.integers(2):
+                vals[:: max(1, n // 40)] = rng.choice([I64_MIN, I64_MAX])
+            cmp_ = str(rng.choice(expr_ref.CMP_OPS))
+            lit = [0, 1, -r, r, I64_MIN, I64_MAX, 0.5, -1.5, 2.0, 1e30,
+                   float("inf"), float("-inf"), float("nan")][int(rng.integers(13))]
+            valid, vb = expr_valid(n)
+            if valid is not None and not isinstance(lit, float):
+                vals[~valid] = lit
+            perm, cnt = gq.filter_cmp(dev(vals), cmp_, lit, validity=vb)
+            exp = expr_ref.ref_filter(vals, valid, cmp_, lit, "i64")
+            assert cnt == len(exp)
+            assert (perm.cpu().numpy().view(np.uint32) == exp).all()
+        elif op == "filter_f64":
+            n = expr_n()
+            vals = rng.random(n) * 2 - 1
+            if n:
+                for sp in (0.0, -0.0, np.nan, np.inf, -np.inf, 0.5):
+                    vals[int(rng.integers(n)):: int(rng.integers(5, 60))] = sp
+            cmp_ = str(rng.choice(expr_ref.CMP_OPS))
+            lit = [0.5, 0.0, -0.0, float("inf"), float("-inf"), float("nan"),
+                   float(rng.random() * 2 - 1)][int(rng.integers(7))]
+            valid, vb = expr_valid(n)
+            perm, cnt = gq.filter_cmp(dev(vals), cmp_, lit, validity=vb)
+            exp = expr_ref.ref_filter(vals, valid, cmp_, lit, "f64")
+            assert cnt == len(exp)
+            assert (perm.cpu().numpy().view(np.uint32) == exp).all()
+        elif op == "project":
+            n = expr_n()
+            dt = str(rng.choice(["i64", "f64"]))
+            bop = str(rng.choice(expr_ref.BIN_OPS))
+            if dt == "i64":
+                a = rng.integers(-100, 101, size=n, dtype=np.int64)
+                b = rng.integers(-10, 11, size=n, dtype=np.int64)
+                specials = [I64_MIN, I64_MAX, -1, 0, 2]
+                lit = int(rng.choice([-1, 0, 3, 100])) if rng.integers(4) \
+                    else [I64_MIN, I64_MAX][int(rng.integers(2))]
+            else:
+                a = rng.random(n) * 200 - 100
+                b = rng.random(n) * 20 - 10
+                specials = [0.0, -0.0, np.inf, -np.inf, np.nan, 5e-324]
+                lit = [2.5, 0.0, -0.0, float("inf"), float("nan"),
+                       5e-324][int(rng.integers(6))]
+            if n:
+                for sp in specials:
+                    a[int(rng.integers(n)):: int(rng.integers(5, 60))] = sp
+                    b[int(rng.integers(n)):: int(rng.integers(5, 60))] = sp
+            av, avb = expr_valid(n)
+            if av is not None:
+                a[~av] = specials[0]
+            if rng.integers(2):          # column-column
+                bv, bvb = expr_valid(n)
+                if bv is not None:
+                    b[~bv] = 0
+                out, bits = gq.project_binop_nullable(
+                    dev(a), bop, b=dev(b), a_validity=avb, b_validity=bvb)
+                ev, evalid = expr_ref.ref_binop(a, av, bop, b, bv, dt)
+                nullable = av is not None or bv is not None or bop == "/"
+            else:                        # column-literal
+                out, bits = gq.project_binop_nullable(
+                    dev(a), bop, literal=lit, a_validity=avb)
+                ev, evalid = expr_ref.ref_binop(a, av, bop, lit, None, dt)
+                nullable = av is not None or bop == "/"
+            assert (bits is not None) == nullable
+            if bits is not None:
+                assert (unpack(bits, n) == evalid).all()
+            else:
+                assert evalid.all()
+            assert same_values(out.cpu().numpy(), ev, evalid)
+        elif op == "sort_i64":
             r = int(rng.choice([0, 1, 10, 1000, 10**6, 2**62]))
             keys = oracle.gen_i64(seed, n, range_=r)
             desc = bool(rng.integers(2))
