@@ -329,6 +329,62 @@ int gpuq_join_probe_i64(void* stream, int64_t probe_rows, gpuq_col probe_key,
                         int64_t out_cap, int64_t* out_nmatches);
 
 /* ---------------------------------------------------------------- */
+/* COMPOSITE-KEY HASH JOIN — equi-join on a key tuple, the general   */
+/* HashJoin case (joins/HashJoin.scala leftKeys/rightKeys:           */
+/* Seq[Expression]); the single-key entry points above are its       */
+/* LongHashedRelation special case. 1 <= nkeys <= 4; every key       */
+/* column is GPUQ_INT64 with optional validity. A row with a NULL in */
+/* ANY key column never matches (no null-safe <=>). -1, 0 and        */
+/* INT64_MIN are ordinary key values. Emission order is              */
+/* nondeterministic.                                                 */
+/* ---------------------------------------------------------------- */
+
+/* Table + chains + matched bits for build_rows rows at the given capacity.
+ * Pure arithmetic (no device query); 0 for arguments out of range. The
+ * workspace must be 64-byte aligned and stay alive through the probes. */
+int64_t gpuq_join_keys_workspace_bytes(int64_t build_rows, int64_t capacity, int32_t nkeys);
+
+/* Build the table over the build-side key columns: one slot per distinct
+ * tuple, duplicates chained. capacity: a power of two GREATER than the
+ * number of distinct non-NULL build tuples (callers use >= 2*build_rows);
+ * build_rows <= 0x7FFFFFFE. A table that cannot seat every tuple gives up
+ * after `capacity` slot visits and returns GPUQ_ERR_OVERFLOW (bounded, no
+ * hang); the workspace is then unusable until rebuilt. Bad nkeys, a
+ * non-power-of-two capacity or a non-int64 key return GPUQ_ERR_INVALID
+ * before anything is launched. Resets the matched bits. */
+int gpuq_join_build_keys(void* stream, int64_t build_rows,
+                         const gpuq_col* build_keys, int32_t nkeys,
+                         void* workspace, int64_t capacity);
+
+/* Probe one batch: emits (probe_rid, build_rid) uint32 pairs exactly as
+ * gpuq_join_probe_i64_typed does — *out_nmatches is always set; if it
+ * exceeds out_capacity nothing is written past out_capacity and
+ * GPUQ_ERR_OVERFLOW is returned (call again with bigger buffers; setting
+ * matched bits twice is harmless). join_type: 0=Inner, 1=probe-side Outer,
+ * 2=LeftSemi, 3=LeftAnti, 4=FullOuter probe half (as 1, and sets the
+ * matched bit of every build row it pairs). Type 4 does NOT emit unmatched
+ * build rows: a probe side arriving in several batches calls this once per
+ * batch and gpuq_join_keys_unmatched_build once at the end. Type 5
+ * (null-aware anti) is single-key only (isNullAwareAntiJoin requires
+ * leftKeys.length == 1) and returns GPUQ_ERR_INVALID, like every other bad
+ * argument, before anything is launched. */
+int gpuq_join_probe_keys(void* stream, int64_t probe_rows,
+                         const gpuq_col* probe_keys, int32_t nkeys,
+                         void* workspace, int64_t capacity, int64_t build_rows,
+                         int32_t join_type,
+                         uint32_t* out_probe_rid, uint32_t* out_build_rid,
+                         int64_t out_capacity, int64_t* out_nmatches);
+
+/* FullOuter second half: one (0xFFFFFFFF, build_rid) pair per build row
+ * whose matched bit is clear after the type-4 probes so far — NULL-key
+ * build rows included (never inserted, so never matched). Same overflow
+ * contract as the probe; build_rows entries always suffice. */
+int gpuq_join_keys_unmatched_build(void* stream, void* workspace, int64_t capacity,
+                                   int64_t build_rows, int32_t nkeys,
+                                   uint32_t* out_probe_rid, uint32_t* out_build_rid,
+                                   int64_t out_capacity, int64_t* out_nrows);
+
+/* ---------------------------------------------------------------- */
 /* FILTER / PROJECT — SURVEY §8(f).2: FilterExec / ProjectExec on    */
 /* columnar batches, so multi-operator plans stay on-device.         */
 /* Filter: single comparison col OP literal; WHERE keeps only TRUE   */

@@ -2600,6 +2600,418 @@ extern "C" int gpuq_join_probe_i64(void* stream, int64_t prows, gpuq_col pkey,
                                    out_p, out_b, out_cap, out_nmatches);
 }
 
+/* ============ composite-key hash join (multi-column equi-join) ============ */
+/*
+ * Equi-join on a key tuple (k1..kK), K <= 4 int64 columns with independent
+ * NULLability — HashJoin.scala joins on leftKeys/rightKeys: Seq[Expression];
+ * the single-long LongHashedRelation above is its special case.
+ *
+ * One open-address slot per DISTINCT tuple, the tuple stored in the slot:
+ *   { u64 sig; u32 head; u32 pad; i64 key[K] }
+ * with the stride rounded up to 32 B (K <= 2) or 64 B (K 3-4), so a slot
+ * never straddles a 64 B line: random probes pay per line touched, not per
+ * byte (profiles/round2_pmc_fetch.txt), and a probe that finds its tuple has
+ * touched exactly one. Duplicates chain through next[] off the slot's head
+ * word exactly as in the single-key join (join_push_head, JOIN_MULTI,
+ * JOIN_NIL).
+ *
+ * Hashing is the composite aggregate's scheme: slot index from the
+ * seed-chained Murmur3 over the tuple, 64-bit signature from a splitmix
+ * chain, EMPTY/PENDING reserved signature values real signatures are
+ * remapped away from — no special slots, -1 / 0 / INT64_MIN are ordinary
+ * key values. Build claims a slot with CAS(sig: EMPTY->PENDING), stores the
+ * tuple, then publishes the signature (see k_joink_build for the ordering);
+ * a signature hit is verified against the stored tuple, so signature
+ * collisions cost probes, never correctness.
+ * A row with a NULL in ANY key column is never inserted and never matches
+ * (equi-join keys; null-safe <=> is not supported).
+ */
+
+#define JOINK_MAX_KEYS 4
+#define JOINK_EMPTY 0ULL
+#define JOINK_PENDING 1ULL
+#define JOINK_SPIN_LIMIT (1u << 22)
+#define JOINK_HEAD_INIT 0x00000000FFFFFFFFULL   /* head = JOIN_NIL, pad = 0 */
+
+struct joink_cols { const int64_t* k[JOINK_MAX_KEYS]; const uint8_t* v[JOINK_MAX_KEYS]; };
+
+/* j.cursor: output reservation (shared with k_join_unmatched_build);
+ * overflow: 1 = table full, 2 = a PENDING slot was never published */
+struct joink_sp { join_sp j; unsigned long long overflow; };
+
+/* slot stride in u64 words: 32 B for K <= 2, 64 B for K 3-4 */
+static int joink_stride_words(int nkeys) { return nkeys <= 2 ? 4 : 8; }
+
+struct joink_ws {
+  unsigned long long* slots;   /* cap slots of joink_stride_words() u64 */
+  unsigned int* next;
+  unsigned long long* matched; /* build-row matched bits (full outer) */
+  joink_sp* sp;
+};
+
+/* pure arithmetic (no device query): argument validation and the CPU tests
+ * run without a GPU. slots come first, so they inherit the workspace's
+ * alignment (>= 64 B from any device allocator). */
+static void joink_ws_layout(int64_t cap, int64_t brows, int nkeys, joink_ws* w,
+                            char* base, int64_t* total) {
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += (bytes + 255) & ~255LL;
+    return p;
+  };
+  w->slots = (unsigned long long*)take(cap * 8 * joink_stride_words(nkeys));
+  w->next = (unsigned int*)take(brows * 4);
+  w->matched = (unsigned long long*)take(((brows + 63) / 64) * 8);
+  w->sp = (joink_sp*)take(sizeof(joink_sp));
+  *total = off;
+}
+
+extern "C" int64_t gpuq_join_keys_workspace_bytes(int64_t brows, int64_t cap,
+                                                  int32_t nkeys) {
+  if (brows < 0 || cap <= 0 || nkeys < 1 || nkeys > JOINK_MAX_KEYS) return 0;
+  joink_ws w; int64_t total;
+  joink_ws_layout(cap, brows, nkeys, &w, nullptr, &total);
+  return total;
+}
+
+/* shared argument checks; all of them run before any HIP call */
+static int joink_check_table(const char* who, int32_t nkeys, int64_t cap,
+                             int64_t brows) {
+  if (nkeys < 1 || nkeys > JOINK_MAX_KEYS)
+    FAIL(GPUQ_ERR_INVALID, "%s: nkeys %d not in [1,%d]", who, nkeys, JOINK_MAX_KEYS);
+  if (cap <= 0 || (cap & (cap - 1)))
+    FAIL(GPUQ_ERR_INVALID, "%s: capacity %lld not a power of two", who, (long long)cap);
+  if (brows < 0 || brows > 0x7FFFFFFELL)
+    FAIL(GPUQ_ERR_INVALID, "%s: build rows %lld do not fit 31-bit rowids", who,
+         (long long)brows);
+  return GPUQ_OK;
+}
+
+static int joink_check_cols(const char* who, const gpuq_col* cols, int32_t nkeys,
+                            joink_cols* kc) {
+  if (!cols) FAIL(GPUQ_ERR_INVALID, "%s: key columns missing", who);
+  for (int c = 0; c < nkeys; c++) {
+    if (cols[c].dtype != GPUQ_INT64)
+      FAIL(GPUQ_ERR_INVALID, "%s: key col %d must be int64", who, c);
+    kc->k[c] = (const int64_t*)cols[c].data;
+    kc->v[c] = cols[c].validity;
+  }
+  return GPUQ_OK;
+}
+
+/* row i's tuple, slot hash and signature; false if any key column is NULL */
+DEV bool joink_load(const joink_cols& kc, int nkeys, int64_t i, int64_t* key,
+                    uint32_t* slot_hash, unsigned long long* sig) {
+  uint32_t h = 42;
+  uint64_t s = 0x243F6A8885A308D3ULL;
+#pragma unroll
+  for (int c = 0; c < JOINK_MAX_KEYS; c++) {
+    if (c < nkeys) {
+      if (!bit_valid(kc.v[c], i)) return false;
+      int64_t k = kc.k[c][i];
+      key[c] = k;
+      h = (uint32_t)mm3_hash_long(k, (int32_t)h);
+      s = splitmix64((s ^ (uint64_t)k) + (uint64_t)c);
+    }
+  }
+  if (s == JOINK_EMPTY || s == JOINK_PENDING) s = 2;
+  *slot_hash = h; *sig = s;
+  return true;
+}
+
+__global__ void k_joink_init(int64_t cap, int sw, unsigned long long* slots,
+                             joink_sp* sp) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t gs = (int64_t)gridDim.x * blockDim.x;
+  for (; i < cap; i += gs) {
+    slots[i * sw] = JOINK_EMPTY;
+    slots[i * sw + 1] = JOINK_HEAD_INIT;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    sp->j.m1_head = JOIN_NIL; sp->j.bucketed = 0; sp->j.cursor = 0;
+    sp->overflow = 0;
+  }
+}
+
+/* Claim/publish as in k_aggk_build: one attempt per loop iteration, so a
+ * lane spinning on PENDING never starves the publisher in its own wave (the
+ * publisher's branch runs between iterations). Unlike the aggregate the
+ * whole loop is bounded: `cap` slot visits without a home means the table
+ * is full, JOINK_SPIN_LIMIT reloads of one PENDING word means its publisher
+ * is gone — both set the overflow word and give up.
+ * Publication without a per-claim L2 write-back: the tuple words are stored
+ * with agent-scope atomics (write-through), the storing lane's wave drains
+ * them (vmcnt(0)) and only then stores the signature, also agent-scope; a
+ * reader polls the signature relaxed and, on a hit, takes ONE agent acquire
+ * before loading the tuple with agent-scope atomic loads. A release on the
+ * signature store instead (buffer_wbl2 per claimed slot, plus an L1
+ * invalidate per poll from acquire loads) measured 20x the single-key
+ * build at 2M distinct tuples (profiles/README.md). */
+__global__ __launch_bounds__(256)
+void k_joink_build(int64_t n, joink_cols kc, int nkeys, int sw,
+                   unsigned long long* slots, unsigned int* next,
+                   joink_sp* sp, int64_t cap_mask) {
+  int64_t base = (int64_t)blockIdx.x * JOIN_CHUNK;
+  for (int r = 0; r < JOIN_CHUNK / 256; r++) {
+    int64_t i = base + r * 256 + threadIdx.x;
+    if (i >= n) return;
+    int64_t key[JOINK_MAX_KEYS];
+    uint32_t h; unsigned long long mysig;
+    if (!joink_load(kc, nkeys, i, key, &h, &mysig)) continue;  /* NULL never matches */
+    uint64_t slot = h & (uint64_t)cap_mask;
+    int64_t visits = 0;
+    uint32_t spins = 0;
+    unsigned long long* sl;
+    for (;;) {
+      sl = slots + slot * sw;
+      unsigned long long cur = __hip_atomic_load(sl, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT);
+      if (cur == JOINK_EMPTY) {
+        unsigned long long prev = atomicCAS(sl, JOINK_EMPTY, JOINK_PENDING);
+        if (prev == JOINK_EMPTY) {
+#pragma unroll
+          for (int c = 0; c < JOINK_MAX_KEYS; c++)
+            if (c < nkeys)
+              __hip_atomic_store(&sl[2 + c], (unsigned long long)key[c],
+                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          /* drain the write-through tuple stores, then publish */
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __hip_atomic_store(sl, mysig, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          break;
+        }
+        cur = JOINK_PENDING;  /* lost the claim: the word is PENDING or a sig now */
+      }
+      if (cur == JOINK_PENDING) {
+        if (++spins > JOINK_SPIN_LIMIT) { atomicMax(&sp->overflow, 2ull); return; }
+        continue;  /* publisher runs between iterations */
+      }
+      if (cur == mysig) {
+        /* acquire only on a signature hit, never per poll */
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        bool eq = true;
+#pragma unroll
+        for (int c = 0; c < JOINK_MAX_KEYS; c++)
+          if (c < nkeys)
+            eq = eq && __hip_atomic_load(&sl[2 + c], __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT) ==
+                           (unsigned long long)key[c];
+        if (eq) break;
+      }
+      slot = (slot + 1) & (uint64_t)cap_mask;
+      if (++visits > cap_mask) { atomicMax(&sp->overflow, 1ull); return; }
+    }
+    join_push_head((unsigned int*)(sl + 1), (unsigned int)i, next);
+  }
+}
+
+/* Same structure as k_join_probe: phase A looks every row up (match counts
+ * and the first two matches stay in registers), phase B makes ONE output
+ * reservation per block. JT as there, 0-4; a probe row with a NULL in any
+ * key column has zero matches. The table was published by an earlier
+ * launch, so plain loads suffice. */
+template <int JT>
+__global__ __launch_bounds__(256)
+void k_joink_probe(int64_t n, joink_cols kc, int nkeys, int sw,
+                   const unsigned long long* slots, const unsigned int* next,
+                   joink_sp* sp, int64_t cap_mask,
+                   uint32_t* out_p, uint32_t* out_b, int64_t out_cap,
+                   unsigned long long* matched) {
+  constexpr int ROUNDS = JOIN_CHUNK / 256;
+  __shared__ unsigned long long block_base;
+  __shared__ uint32_t wtot[256 / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int64_t base = (int64_t)blockIdx.x * JOIN_CHUNK;
+
+  uint32_t cnt[ROUNDS];
+  unsigned int c0[ROUNDS], c1[ROUNDS];
+  uint32_t lane_total = 0;
+  for (int r = 0; r < ROUNDS; r++) {
+    int64_t i = base + r * 256 + threadIdx.x;
+    unsigned int head = JOIN_NIL;
+    int64_t key[JOINK_MAX_KEYS];
+    uint32_t h; unsigned long long mysig;
+    if (i < n && joink_load(kc, nkeys, i, key, &h, &mysig)) {
+      uint64_t slot = h & (uint64_t)cap_mask;
+      /* bounded like the build: a (contract-violating) full table ends the
+       * walk after cap visits instead of circling */
+      for (int64_t visits = 0; visits <= cap_mask; visits++) {
+        const unsigned long long* sl = slots + slot * sw;
+        unsigned long long cur = sl[0];
+        if (cur == JOINK_EMPTY) break;
+        if (cur == mysig) {
+          bool eq = true;
+#pragma unroll
+          for (int c = 0; c < JOINK_MAX_KEYS; c++)
+            if (c < nkeys) eq = eq && sl[2 + c] == (unsigned long long)key[c];
+          if (eq) { head = (unsigned int)sl[1]; break; }
+        }
+        slot = (slot + 1) & (uint64_t)cap_mask;
+      }
+    }
+    cnt[r] = 0; c0[r] = JOIN_NIL; c1[r] = JOIN_NIL;
+    if (head != JOIN_NIL) {
+      if (!(head & JOIN_MULTI)) {
+        c0[r] = head; cnt[r] = 1;
+        if (JT == 4) atomicOr(&matched[head >> 6], 1ull << (head & 63));
+      } else {
+        for (unsigned int b = head & ~JOIN_MULTI; b != JOIN_NIL; b = next[b]) {
+          if (cnt[r] == 0) c0[r] = b; else if (cnt[r] == 1) c1[r] = b;
+          cnt[r]++;
+          if (JT == 4) atomicOr(&matched[b >> 6], 1ull << (b & 63));
+        }
+      }
+    }
+    if (JT == 0) lane_total += cnt[r];
+    else if (i < n) lane_total += jt_emit_count(JT, cnt[r]);
+  }
+  /* phase B: block-level reservation (emit order within the block is
+   * arbitrary — join output order is nondeterministic by contract) */
+  uint32_t incl = wave_inclusive_scan(lane_total);
+  if (lane == WAVE - 1) wtot[wave] = incl;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (int w = 0; w < 256 / WAVE; w++) {
+      uint32_t t = wtot[w]; wtot[w] = tot; tot += t;
+    }
+    block_base = tot ? atomicAdd(&sp->j.cursor, (unsigned long long)tot) : 0;
+  }
+  __syncthreads();
+  int64_t o = (int64_t)block_base + wtot[wave] + (incl - lane_total);
+  for (int r = 0; r < ROUNDS; r++) {
+    int64_t i = base + r * 256 + threadIdx.x;
+    if (JT != 0) {
+      if (i >= n || !jt_emit_count(JT, cnt[r])) continue;
+      if (JT == 2 || JT == 3 || cnt[r] == 0) {
+        /* semi/anti emit the probe row once; outer's unmatched row pairs
+         * with NIL (NULL build columns downstream) */
+        if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = JOIN_NIL; }
+        o++;
+        continue;
+      }
+    }
+    if (!cnt[r]) continue;
+    if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = c0[r]; }
+    o++;
+    if (cnt[r] >= 2) {
+      if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = c1[r]; }
+      o++;
+      unsigned int b = (cnt[r] > 2) ? next[c1[r]] : JOIN_NIL;
+      for (uint32_t j = 2; j < cnt[r]; j++, b = next[b], o++) {
+        if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = b; }
+      }
+    }
+  }
+}
+
+extern "C" int gpuq_join_build_keys(void* stream, int64_t brows,
+                                    const gpuq_col* build_keys, int32_t nkeys,
+                                    void* workspace, int64_t cap) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = joink_check_table("join_keys build", nkeys, cap, brows)) return rc;
+  joink_cols kc = {};
+  if (int rc = joink_check_cols("join_keys build", build_keys, nkeys, &kc)) return rc;
+  joink_ws w; int64_t need;
+  joink_ws_layout(cap, brows, nkeys, &w, (char*)workspace, &need);
+  int sw = joink_stride_words(nkeys);
+  k_joink_init<<<grid1d(cap), 256, 0, s>>>(cap, sw, w.slots, w.sp);
+  HIP_TRY(hipGetLastError());
+  if (brows == 0) return GPUQ_OK;
+  HIP_TRY(hipMemsetAsync(w.matched, 0, ((brows + 63) / 64) * 8, s));
+  int64_t nchunks = (brows + JOIN_CHUNK - 1) / JOIN_CHUNK;
+  { hipEvent_t _pe = prof_begin(s);
+  k_joink_build<<<dim3((uint32_t)nchunks), 256, 0, s>>>(
+      brows, kc, nkeys, sw, w.slots, w.next, w.sp, cap - 1);
+  prof_end("join_keys_build", s, _pe); }
+  HIP_TRY(hipGetLastError());
+  joink_sp hsp;
+  HIP_TRY(hipMemcpyAsync(&hsp, w.sp, sizeof(hsp), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (hsp.overflow == 1)
+    FAIL(GPUQ_ERR_OVERFLOW, "join_keys build: hash table overflow (capacity %lld)",
+         (long long)cap);
+  if (hsp.overflow)
+    FAIL(GPUQ_ERR_OVERFLOW, "join_keys build: gave up on an unpublished slot "
+         "(capacity %lld)", (long long)cap);
+  return GPUQ_OK;
+}
+
+extern "C" int gpuq_join_probe_keys(void* stream, int64_t prows,
+                                    const gpuq_col* probe_keys, int32_t nkeys,
+                                    void* workspace, int64_t cap, int64_t brows,
+                                    int32_t join_type,
+                                    uint32_t* out_p, uint32_t* out_b,
+                                    int64_t out_cap, int64_t* out_nmatches) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = joink_check_table("join_keys probe", nkeys, cap, brows)) return rc;
+  if (join_type == 5)
+    FAIL(GPUQ_ERR_INVALID, "join_keys probe: the null-aware anti join (type 5) "
+         "is single-key only");
+  if (join_type < 0 || join_type > 4)
+    FAIL(GPUQ_ERR_INVALID, "join_keys probe: bad join_type %d", join_type);
+  if (prows < 0 || prows > 0xFFFFFFFELL)
+    FAIL(GPUQ_ERR_INVALID, "join_keys probe: probe rows %lld do not fit 32-bit rowids",
+         (long long)prows);
+  joink_cols kc = {};
+  if (int rc = joink_check_cols("join_keys probe", probe_keys, nkeys, &kc)) return rc;
+  joink_ws w; int64_t need;
+  joink_ws_layout(cap, brows, nkeys, &w, (char*)workspace, &need);
+  HIP_TRY(hipMemsetAsync(&w.sp->j.cursor, 0, 8, s));
+  if (prows > 0) {
+    int sw = joink_stride_words(nkeys);
+    dim3 jg((uint32_t)((prows + JOIN_CHUNK - 1) / JOIN_CHUNK));
+    hipEvent_t _pe = prof_begin(s);
+#define JKP(JT) k_joink_probe<JT><<<jg, 256, 0, s>>>( \
+        prows, kc, nkeys, sw, w.slots, w.next, w.sp, cap - 1, out_p, out_b, \
+        out_cap, w.matched)
+    switch (join_type) {
+      case 1: JKP(1); break;
+      case 2: JKP(2); break;
+      case 3: JKP(3); break;
+      case 4: JKP(4); break;
+      default: JKP(0); break;
+    }
+#undef JKP
+    prof_end("join_keys_probe", s, _pe);
+    HIP_TRY(hipGetLastError());
+  }
+  joink_sp hsp;
+  HIP_TRY(hipMemcpyAsync(&hsp, w.sp, sizeof(hsp), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *out_nmatches = (int64_t)hsp.j.cursor;
+  if ((int64_t)hsp.j.cursor > out_cap)
+    FAIL(GPUQ_ERR_OVERFLOW, "join_keys probe: %lld matches exceed out_cap %lld",
+         (long long)hsp.j.cursor, (long long)out_cap);
+  return GPUQ_OK;
+}
+
+extern "C" int gpuq_join_keys_unmatched_build(void* stream, void* workspace,
+                                              int64_t cap, int64_t brows,
+                                              int32_t nkeys,
+                                              uint32_t* out_p, uint32_t* out_b,
+                                              int64_t out_cap, int64_t* out_nrows) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = joink_check_table("join_keys unmatched", nkeys, cap, brows)) return rc;
+  joink_ws w; int64_t need;
+  joink_ws_layout(cap, brows, nkeys, &w, (char*)workspace, &need);
+  HIP_TRY(hipMemsetAsync(&w.sp->j.cursor, 0, 8, s));
+  if (brows > 0) {
+    k_join_unmatched_build<<<grid1d(brows), 256, 0, s>>>(
+        brows, w.matched, nullptr, &w.sp->j, out_p, out_b, out_cap);
+    HIP_TRY(hipGetLastError());
+  }
+  joink_sp hsp;
+  HIP_TRY(hipMemcpyAsync(&hsp, w.sp, sizeof(hsp), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *out_nrows = (int64_t)hsp.j.cursor;
+  if ((int64_t)hsp.j.cursor > out_cap)
+    FAIL(GPUQ_ERR_OVERFLOW, "join_keys unmatched: %lld rows exceed out_cap %lld",
+         (long long)hsp.j.cursor, (long long)out_cap);
+  return GPUQ_OK;
+}
+
 /* ---- partitioned aggregation (mid/high cardinality) ----
  * The direct table is atomic-throughput-bound (~22 G f64-adds/s at 10M
  * groups, tools/diag_hash.py). Round-2 design: ONE non-stable 13-bit

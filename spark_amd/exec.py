@@ -163,15 +163,41 @@ class HashAggregateExec(_CpuNode):
         return out
 
 
-class ShuffledHashJoinExec(_CpuNode):
+def _join_key_tuples(left_key, right_key):
+    """Join keys are one column name or a sequence of 1-4 names, the same
+    count on both sides (HashJoin.scala leftKeys/rightKeys: Seq[Expression];
+    the engine's composite table holds up to 4 int64 columns)."""
+    lk = (left_key,) if isinstance(left_key, str) else tuple(left_key)
+    rk = (right_key,) if isinstance(right_key, str) else tuple(right_key)
+    assert len(lk) == len(rk), f"join key counts differ: {lk} vs {rk}"
+    assert 1 <= len(lk) <= 4, f"join on {len(lk)} key columns (1-4 supported)"
+    return lk, rk
+
+
+class _JoinKeys:
+    """left_key / right_key keep whatever the constructor was given (a name
+    or a sequence); left_keys / right_keys are always tuples."""
+
+    @property
+    def left_keys(self):
+        return _join_key_tuples(self.left_key, self.right_key)[0]
+
+    @property
+    def right_keys(self):
+        return _join_key_tuples(self.left_key, self.right_key)[1]
+
+
+class ShuffledHashJoinExec(_JoinKeys, _CpuNode):
     """join_type: "inner" | "left_outer" | "right_outer" | "left_semi" |
     "left_anti" (ShuffledHashJoinExec.scala joinType; the preserved side
     must stream, so left-preserving types build on the right and
-    vice versa)."""
+    vice versa). left_key / right_key: a column name, or 1-4 names per side
+    for a composite equi-join."""
 
-    def __init__(self, left_key: str, right_key: str, build_side: str,
+    def __init__(self, left_key, right_key, build_side: str,
                  left, right, join_type: str = "inner"):
         super().__init__(left, right)
+        _join_key_tuples(left_key, right_key)
         self.left_key, self.right_key, self.build_side = left_key, right_key, build_side
         self.join_type = join_type
 
@@ -182,16 +208,17 @@ class ShuffledHashJoinExec(_CpuNode):
         return self.children[0].output + self.children[1].output
 
 
-class SortMergeJoinExec(_CpuNode):
+class SortMergeJoinExec(_JoinKeys, _CpuNode):
     """CPU placeholder (joins/SortMergeJoinExec.scala:135). The GPU plan
     replaces SMJ with the hash join — both fill the same equi-join plan slot
     with identical ClusteredDistribution requirements (ShuffledJoin.scala:
     57-69), and on GPU the hash build/probe dominates sort+merge for
     co-partitioned batches."""
 
-    def __init__(self, left_key: str, right_key: str, left, right,
+    def __init__(self, left_key, right_key, left, right,
                  join_type: str = "inner"):
         super().__init__(left, right)
+        _join_key_tuples(left_key, right_key)
         self.left_key, self.right_key = left_key, right_key
         self.join_type = join_type
 
@@ -208,8 +235,8 @@ class SortMergeJoinExec(_CpuNode):
         if self.join_type == "full_outer":
             return []
         if self.join_type == "right_outer":
-            return [SortOrder(self.right_key)]
-        return [SortOrder(self.left_key)]
+            return [SortOrder(k) for k in self.right_keys]
+        return [SortOrder(k) for k in self.left_keys]
 
 
 class ShuffleExchangeExec(_CpuNode):
@@ -257,15 +284,18 @@ class RangeExec(_CpuNode):
         return [self.name]
 
 
-class BroadcastHashJoinExec(_CpuNode):
-    """CPU placeholder (joins/BroadcastHashJoinExec.scala:40): inner
-    equi-join with a broadcast (small) build side."""
+class BroadcastHashJoinExec(_JoinKeys, _CpuNode):
+    """CPU placeholder (joins/BroadcastHashJoinExec.scala:40): equi-join
+    with a broadcast (small) build side; inner unless join_type says
+    otherwise."""
 
-    def __init__(self, left_key: str, right_key: str, build_side: str,
-                 left, right):
+    def __init__(self, left_key, right_key, build_side: str,
+                 left, right, join_type: str = "inner"):
         super().__init__(left, right)
         assert build_side in ("left", "right")
+        _join_key_tuples(left_key, right_key)
         self.left_key, self.right_key, self.build_side = left_key, right_key, build_side
+        self.join_type = join_type
 
     @property
     def output(self):
@@ -964,23 +994,29 @@ class GpuShuffleExchangeExec(SparkPlan):
             yield ColumnarBatch(out, validity=validity or None)
 
 
-class GpuShuffledHashJoinExec(SparkPlan):
+class GpuShuffledHashJoinExec(_JoinKeys, SparkPlan):
     """Replaces ShuffledHashJoinExec inner join
     (ShuffledHashJoinExec.scala:103-132). Both children must already be
     clustered on the join key (ShuffledJoin.scala:57-69) — i.e. fed by (our)
-    exchanges, as EnsureRequirements would arrange."""
+    exchanges, as EnsureRequirements would arrange. One key column runs the
+    single-key (LongHashedRelation-style) kernels; 2-4 key columns run the
+    composite-key table (gpuq_join_*_keys)."""
 
-    def __init__(self, left_key: str, right_key: str, build_side: str,
+    def __init__(self, left_key, right_key, build_side: str,
                  left, right, join_type: str = "inner",
                  null_aware_anti: bool = False):
         super().__init__(left, right)
         assert build_side in ("left", "right")
         assert join_type in ("inner", "left_outer", "right_outer",
                              "left_semi", "left_anti", "full_outer")
+        lk, _ = _join_key_tuples(left_key, right_key)
         # NOT IN rewrite (BroadcastHashJoinExec.scala:48,137
         # isNullAwareAntiJoin): empty build -> all probe rows; any NULL
         # build key -> empty result; NULL probe keys are filtered
         assert not null_aware_anti or join_type == "left_anti"
+        # isNullAwareAntiJoin requires leftKeys.length == 1
+        assert not null_aware_anti or len(lk) == 1, \
+            "null-aware anti join is single-key only"
         self.null_aware_anti = null_aware_anti
         # the preserved/streamed side must be the PROBE side
         # (HashJoin.scala buildSide constraints; full outer preserves both
@@ -1003,8 +1039,85 @@ class GpuShuffledHashJoinExec(SparkPlan):
         return True
 
     def required_child_distribution(self):
-        return [Distribution("clustered", (self.left_key,)),
-                Distribution("clustered", (self.right_key,))]
+        return [Distribution("clustered", self.left_keys),
+                Distribution("clustered", self.right_keys)]
+
+    def _join_output(self, build, probe_cols, probe_validity, op, ob):
+        """One output batch from matched (probe_rid, build_rid) pairs: build
+        columns gathered by ob (NIL -> NULL for the outer types), probe
+        columns by op (NIL -> NULL for full outer); a probe column whose
+        name the build side already uses gets a `#probe` suffix."""
+        from . import gpuq
+        semi = self.join_type in ("left_semi", "left_anti")
+        outer = self.join_type in ("left_outer", "right_outer", "full_outer")
+        full = self.join_type == "full_outer"
+        cols, validity = {}, {}
+        if not semi:
+            for name, t in build.columns().items():
+                if outer:
+                    # unmatched probe rows pair with NIL -> NULL build
+                    cols[name], validity[name] = gpuq.gather_nullable(
+                        t, ob, validity=build.validity(name))
+                else:
+                    cols[name] = gpuq.gather(t, ob)
+                    v = build.validity(name)
+                    if v is not None:
+                        validity[name] = gpuq.gather_bits(v, ob)
+        for name, t in probe_cols.items():
+            v = probe_validity.get(name)
+            if name in cols:
+                name = f"{name}#probe"
+            if full:
+                # build-side unmatched rows carry NIL probe rids
+                cols[name], validity[name] = gpuq.gather_nullable(
+                    t, op, validity=v)
+            else:
+                cols[name] = gpuq.gather(t, op)
+                if v is not None:
+                    validity[name] = gpuq.gather_bits(v, op)
+        return ColumnarBatch(cols, validity=validity or None)
+
+    def _execute_composite(self, gpuq, build, bkeys, pkeys, jt, probe_iter):
+        """2-4 key columns: one composite-key table over the concatenated
+        build side, probed batch-at-a-time. Full outer emits the unmatched
+        build rows ONCE, after the last probe batch, from the matched bits
+        the probes accumulated."""
+        bn = build.num_rows()
+        nkeys = len(bkeys)
+        cap = 1 << max(4, int(bn * 2 - 1).bit_length() if bn else 4)
+        ws = gpuq.join_build_keys(
+            [build.column(k) for k in bkeys], cap,
+            key_validities=[build.validity(k) for k in bkeys])
+        full = self.join_type == "full_outer"
+        probe_dtypes = None
+        for probe in probe_iter:
+            pk = [probe.column(k) for k in pkeys]
+            pkv = [probe.validity(k) for k in pkeys]
+            out_cap = max(int(probe.num_rows() * 2) + 64, 64)
+            while True:
+                op, ob, nm = gpuq.join_probe_keys(pk, ws, cap, bn, out_cap,
+                                                  key_validities=pkv,
+                                                  join_type=jt)
+                if op is not None:
+                    break
+                out_cap = nm + 64
+            pcols = probe.columns()
+            probe_dtypes = {n_: t.dtype for n_, t in pcols.items()}
+            out = self._join_output(
+                build, pcols, {n_: probe.validity(n_) for n_ in pcols}, op, ob)
+            probe.close()
+            yield out
+        if full:
+            # the NULL probe columns need the probe schema
+            assert probe_dtypes is not None, \
+                "full outer join over a batchless probe child"
+            op, ob, nu = gpuq.join_keys_unmatched_build(ws, cap, bn, nkeys)
+            if nu:
+                # every op entry is NIL: the one-row sources are never read
+                null_src = {n_: torch.zeros(1, dtype=dt, device=ob.device)
+                            for n_, dt in probe_dtypes.items()}
+                yield self._join_output(build, null_src, {}, op, ob)
+        build.close()
 
     def execute_columnar(self):
         from . import gpuq
@@ -1014,12 +1127,18 @@ class GpuShuffledHashJoinExec(SparkPlan):
         # buildHashedRelation materializes the whole build side per
         # partition: multi-batch children concatenate
         build = concat_batches(build_b)
-        bkey = self.left_key if self.build_side == "left" else self.right_key
-        pkey = self.right_key if self.build_side == "left" else self.left_key
         jt = {"inner": gpuq.JOIN_INNER, "left_outer": gpuq.JOIN_OUTER,
               "right_outer": gpuq.JOIN_OUTER, "left_semi": gpuq.JOIN_SEMI,
               "left_anti": gpuq.JOIN_ANTI,
               "full_outer": gpuq.JOIN_FULL}[self.join_type]
+        bkeys = self.left_keys if self.build_side == "left" else self.right_keys
+        pkeys = self.right_keys if self.build_side == "left" else self.left_keys
+        if len(bkeys) > 1:
+            yield from self._execute_composite(
+                gpuq, build, bkeys, pkeys, jt,
+                self.children[1 - bi].execute_columnar())
+            return
+        bkey, pkey = bkeys[0], pkeys[0]
         bk = build.column(bkey)
         bn = bk.numel()
         if self.null_aware_anti:
@@ -1041,9 +1160,6 @@ class GpuShuffledHashJoinExec(SparkPlan):
             jt = gpuq.JOIN_ANTI_NULLAWARE
         cap = 1 << max(4, int(bn * 2 - 1).bit_length() if bn else 4)
         ws = gpuq.join_build(bk, cap, key_validity=build.validity(bkey))
-        semi = self.join_type in ("left_semi", "left_anti")
-        outer = self.join_type in ("left_outer", "right_outer", "full_outer")
-        full = self.join_type == "full_outer"
         # the probe (streamed) side is consumed batch-at-a-time
         # (ShuffledHashJoinExec.doExecute streams streamedIter)
         for probe in self.children[1 - bi].execute_columnar():
@@ -1056,33 +1172,11 @@ class GpuShuffledHashJoinExec(SparkPlan):
                 if op is not None:
                     break
                 out_cap = nm + 64
-            cols, validity = {}, {}
-            if not semi:
-                for name, t in build.columns().items():
-                    if outer:
-                        # unmatched probe rows pair with NIL -> NULL build
-                        cols[name], validity[name] = gpuq.gather_nullable(
-                            t, ob, validity=build.validity(name))
-                    else:
-                        cols[name] = gpuq.gather(t, ob)
-                        v = build.validity(name)
-                        if v is not None:
-                            validity[name] = gpuq.gather_bits(v, ob)
             pcols = probe.columns()
-            for name, t in pcols.items():
-                v = probe.validity(name)
-                if name in cols:
-                    name = f"{name}#probe"
-                if full:
-                    # build-side unmatched rows carry NIL probe rids
-                    cols[name], validity[name] = gpuq.gather_nullable(
-                        t, op, validity=v)
-                else:
-                    cols[name] = gpuq.gather(t, op)
-                    if v is not None:
-                        validity[name] = gpuq.gather_bits(v, op)
+            out = self._join_output(
+                build, pcols, {n_: probe.validity(n_) for n_ in pcols}, op, ob)
             probe.close()
-            yield ColumnarBatch(cols, validity=validity or None)
+            yield out
         build.close()
 
 
@@ -1287,7 +1381,8 @@ class GpuColumnarRule:
             return GpuBroadcastExchangeExec(*children)
         if isinstance(plan, BroadcastHashJoinExec):
             return GpuBroadcastHashJoinExec(plan.left_key, plan.right_key,
-                                            plan.build_side, *children)
+                                            plan.build_side, *children,
+                                            join_type=plan.join_type)
         plan.children = children
         return plan
 

@@ -134,6 +134,19 @@ def lib() -> ctypes.CDLL:
         L.gpuq_join_probe_i64_typed.argtypes = [vp, i64, _Col, vp, i64, i64, vp,
                                                 i64, i32, vp, vp, i64,
                                                 ctypes.POINTER(i64)]
+        L.gpuq_join_keys_workspace_bytes.restype = i64
+        L.gpuq_join_keys_workspace_bytes.argtypes = [i64, i64, i32]
+        L.gpuq_join_build_keys.restype = i32
+        L.gpuq_join_build_keys.argtypes = [vp, i64, ctypes.POINTER(_Col), i32,
+                                           vp, i64]
+        L.gpuq_join_probe_keys.restype = i32
+        L.gpuq_join_probe_keys.argtypes = [vp, i64, ctypes.POINTER(_Col), i32,
+                                           vp, i64, i64, i32, vp, vp, i64,
+                                           ctypes.POINTER(i64)]
+        L.gpuq_join_keys_unmatched_build.restype = i32
+        L.gpuq_join_keys_unmatched_build.argtypes = [vp, vp, i64, i64, i32,
+                                                     vp, vp, i64,
+                                                     ctypes.POINTER(i64)]
         L.gpuq_gather_nullable.restype = i32
         L.gpuq_gather_nullable.argtypes = [vp, i64, _Col, vp, vp, vp]
         L.gpuq_filter_workspace_bytes.restype = i64
@@ -351,7 +364,71 @@ def join_probe(probe_keys: torch.Tensor, workspace: torch.Tensor, capacity: int,
     return op[:nm.value], ob[:nm.value], nm.value
 
 
-CMP = {"==": 0, "<": 1, "<=": 2, ">": 3, ">=": 4, "!=": 5}
+def _key_cols_arr(key_cols, key_validities):
+    nkeys = len(key_cols)
+    kv = key_validities or [None] * nkeys
+    assert len(kv) == nkeys
+    return (_Col * nkeys)(*[_col(k, v) for k, v in zip(key_cols, kv)])
+
+
+def join_build_keys(key_cols, capacity: int, key_validities=None,
+                    workspace=None):
+    """Composite-key join build over (k1..kK), K <= 4 int64 columns.
+    key_validities: optional list (same length) of validity bitmaps; a row
+    with a NULL in any key column is not inserted. Returns the workspace."""
+    nkeys = len(key_cols)
+    bn = key_cols[0].numel()
+    dev = key_cols[0].device
+    keys_arr = _key_cols_arr(key_cols, key_validities)
+    if workspace is None:
+        workspace = torch.empty(
+            lib().gpuq_join_keys_workspace_bytes(bn, capacity, nkeys),
+            dtype=torch.uint8, device=dev)
+    _check(lib().gpuq_join_build_keys(_stream(), bn, keys_arr, nkeys,
+                                      workspace.data_ptr(), capacity))
+    return workspace
+
+
+def join_probe_keys(key_cols, workspace: torch.Tensor, capacity: int,
+                    build_rows: int, out_cap: int, key_validities=None,
+                    join_type: int = JOIN_INNER):
+    """Probe one batch against a join_build_keys table. Returns (op, ob, n),
+    or (None, None, n) on output overflow, like join_probe. JOIN_FULL sets
+    matched bits only; the unmatched build rows come from
+    join_keys_unmatched_build after the last batch."""
+    nkeys = len(key_cols)
+    pn = key_cols[0].numel()
+    dev = key_cols[0].device
+    keys_arr = _key_cols_arr(key_cols, key_validities)
+    op = torch.empty(out_cap, dtype=torch.int32, device=dev)
+    ob = torch.empty(out_cap, dtype=torch.int32, device=dev)
+    nm = ctypes.c_int64(0)
+    rc = lib().gpuq_join_probe_keys(_stream(), pn, keys_arr, nkeys,
+                                    workspace.data_ptr(), capacity, build_rows,
+                                    join_type, op.data_ptr(), ob.data_ptr(),
+                                    out_cap, ctypes.byref(nm))
+    if rc == 3:  # GPUQ_ERR_OVERFLOW: caller retries with nm.value capacity
+        return None, None, nm.value
+    _check(rc)
+    return op[:nm.value], ob[:nm.value], nm.value
+
+
+def join_keys_unmatched_build(workspace: torch.Tensor, capacity: int,
+                              build_rows: int, nkeys: int):
+    """(NIL, build_rid) pairs for the build rows no JOIN_FULL probe has
+    matched so far. Returns (op, ob, n)."""
+    dev = workspace.device
+    out_cap = max(build_rows, 1)
+    op = torch.empty(out_cap, dtype=torch.int32, device=dev)
+    ob = torch.empty(out_cap, dtype=torch.int32, device=dev)
+    nr = ctypes.c_int64(0)
+    _check(lib().gpuq_join_keys_unmatched_build(
+        _stream(), workspace.data_ptr(), capacity, build_rows, nkeys,
+        op.data_ptr(), ob.data_ptr(), out_cap, ctypes.byref(nr)))
+    return op[:nr.value], ob[:nr.value], nr.value
+
+
+CMP ={"==": 0, "<": 1, "<=": 2, ">": 3, ">=": 4, "!=": 5}
 BINOP = {"+": 0, "-": 1, "*": 2, "/": 3, "rsub": 4}
 
 
