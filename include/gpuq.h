@@ -106,6 +106,19 @@ int gpuq_sort_perm(void* stream, int64_t nrows, gpuq_col key,
                    uint32_t* out_perm, void* out_keys,
                    void* workspace, int64_t workspace_bytes);
 
+/* Pass plan of the last gpuq_sort_perm on the calling thread. With wide keys
+ * the sort radixes only the leading window of active key bytes (enough
+ * changed bits to almost totally order nrows) and resolves the remaining
+ * ties in one streaming pass: window_passes is the number of radix passes
+ * that plan ran and deferred_bytes the number of active low bytes it left to
+ * the tie-fix. deferred_bytes == 0 means the classic all-active-bytes plan
+ * ran (window_passes is 0 then). fell_back == 1 means the tie-fix met an
+ * unsorted run longer than its limit and the sort was redone with the
+ * classic plan; window_passes/deferred_bytes then describe the plan that was
+ * tried. GPUQ_SORT_NO_PREFIX (env, read per call) forces the classic plan.
+ * Any pointer may be NULL. */
+void gpuq_sort_last_plan(int* window_passes, int* deferred_bytes, int* fell_back);
+
 /* out[i] = col[perm[i]] — payload materialization after sort/partition. */
 int gpuq_gather(void* stream, int64_t nrows, gpuq_col col,
                 const uint32_t* perm, void* out);

@@ -166,6 +166,19 @@ DEV double decode_f64(uint64_t e) {
   return __longlong_as_double((long long)(e ^ mask));
 }
 
+/* sort output word for an encoded key: decode_mode 0 keeps the encoded key,
+ * 1 = int64, 2 = float64, +4 = the key was complemented for DESC. Shared by
+ * the fused final scatter pass and the tie-fix kernel. */
+DEV uint64_t sort_out_word(uint64_t kk, int decode_mode) {
+  if (!decode_mode) return kk;
+  uint64_t e = (decode_mode & 4) ? ~kk : kk;
+  if (decode_mode & 2) {
+    uint64_t mask = ((e >> 63) ? 0 : ~0ULL) | SIGNBIT;
+    return e ^ mask;
+  }
+  return e ^ SIGNBIT;
+}
+
 DEV bool bit_valid(const uint8_t* validity, int64_t i) {
   return !validity || ((validity[i >> 3] >> (i & 7)) & 1);
 }
@@ -882,13 +895,7 @@ void k_radix_scatter(int64_t n, const uint64_t* kin, const PayT* iin,
      * Needs odd ITEMS for tolerable LDS bank conflicts (stride 2*ITEMS
      * words, gcd 2 -> 2-way). PayT must be 4 B. */
     auto out_word = [&](uint64_t kk) -> uint64_t {
-      if (!decode_mode) return kk;
-      uint64_t e = (decode_mode & 4) ? ~kk : kk;
-      if (decode_mode & 2) {
-        uint64_t mask = ((e >> 63) ? 0 : ~0ULL) | SIGNBIT;
-        return e ^ mask;
-      }
-      return e ^ SIGNBIT;
+      return sort_out_word(kk, decode_mode);
     };
     uint64_t* kbase = decode_mode ? (uint64_t*)decode_out : kout;
     int j0 = tid * ITEMS;
@@ -923,23 +930,11 @@ void k_radix_scatter(int64_t n, const uint64_t* kin, const PayT* iin,
       int bin = compute_bin<BIN_MODE>(kk, shift, nparts);
       if (RADIX_BITS < 8) bin &= (1 << RADIX_BITS) - 1;
       uint32_t dst = bin_gbase[bin] + (uint32_t)j;
-      uint64_t kv_out;
-      void* kdst;
-      if (decode_mode) {
-        /* final pass: emit the DECODED key column directly (the separate
-           decode kernel and this pass's encoded-key write both disappear) */
-        uint64_t e = (decode_mode & 4) ? ~kk : kk;
-        if (decode_mode & 2) {
-          uint64_t mask = ((e >> 63) ? 0 : ~0ULL) | SIGNBIT;
-          kv_out = e ^ mask;
-        } else {
-          kv_out = e ^ SIGNBIT;
-        }
-        kdst = &((uint64_t*)decode_out)[dst];
-      } else {
-        kv_out = kk;
-        kdst = &kout[dst];
-      }
+      /* final pass: emit the DECODED key column directly (the separate
+         decode kernel and this pass's encoded-key write both disappear) */
+      uint64_t kv_out = sort_out_word(kk, decode_mode);
+      void* kdst = decode_mode ? (void*)&((uint64_t*)decode_out)[dst]
+                               : (void*)&kout[dst];
 #ifdef GPUQ_DRAIN_SC1
       /* write-through: scattered partial-line stores skip the L2
        * write-allocate read-for-ownership (guide: publish-large) */
@@ -1357,6 +1352,121 @@ __global__ void k_decode(int64_t n, const uint64_t* ek, void* out) {
   }
 }
 
+/* ---- prefix plan: tie-fix after the leading-window passes ----
+ * Input: (encoded key, rowid) pairs stably ordered by `key >> shift` (the
+ * leading window; bytes above `shift` outside it are constant). A run is a
+ * maximal stretch of equal `key >> shift`. Runs of up to GPUQ_SORT_TIE_MAX
+ * rows are ranked by (key, position) — inside a run that is the order of the
+ * deferred low bits, ties in input order — and written to run_start + rank.
+ * Longer runs are written in place: fully-equal keys are already in stable
+ * order; a descent inside one raises *overflow and the host redoes the sort
+ * with the full pass list. Runs cross tile edges, so each block stages its
+ * tile with a GPUQ_SORT_TIE_MAX-row halo on both sides. */
+#define GPUQ_SORT_TIE_MAX 32
+#define TIEFIX_BLOCK 256
+#define TIEFIX_ITEMS 8
+#define TIEFIX_TILE (TIEFIX_BLOCK * TIEFIX_ITEMS) /* 2048 */
+
+__global__ __launch_bounds__(TIEFIX_BLOCK)
+void k_sort_tiefix(int64_t n, const uint64_t* kin, const uint32_t* iin,
+                   uint32_t* out_perm, uint64_t* out_keys /* may be null */,
+                   int shift, int decode_mode, unsigned long long* overflow) {
+  constexpr int HALO = GPUQ_SORT_TIE_MAX;
+  __shared__ uint64_t tk[TIEFIX_TILE + 2 * HALO];
+  const int tid = threadIdx.x;
+  const int64_t base = (int64_t)blockIdx.x * TIEFIX_TILE;
+  uint32_t id[TIEFIX_ITEMS];
+  #pragma unroll
+  for (int r = 0; r < TIEFIX_ITEMS; r++) {
+    int64_t i = base + r * TIEFIX_BLOCK + tid;
+    id[r] = i < n ? iin[i] : 0;
+  }
+  for (int j = tid; j < TIEFIX_TILE + 2 * HALO; j += TIEFIX_BLOCK) {
+    int64_t g = base - HALO + j;
+    tk[j] = (g >= 0 && g < n) ? kin[g] : 0;
+  }
+  __syncthreads();
+  #pragma unroll
+  for (int r = 0; r < TIEFIX_ITEMS; r++) {
+    const int j = r * TIEFIX_BLOCK + tid;
+    const int64_t i = base + j;
+    if (i >= n) break;
+    const uint64_t* c = &tk[HALO + j];   /* c[t] = key of row i+t, |t| <= HALO */
+    const uint64_t k = c[0];
+    const uint64_t win = k >> shift;
+    /* bounds come from the row index, never from the staged zero fill */
+    int back = 0, fwd = 0;
+    while (back < HALO && i - back - 1 >= 0 && (c[-back - 1] >> shift) == win) back++;
+    while (fwd < HALO && i + fwd + 1 < n && (c[fwd + 1] >> shift) == win) fwd++;
+    int64_t dst = i;
+    if (back + fwd) {
+      if (back + fwd + 1 <= GPUQ_SORT_TIE_MAX) {
+        /* neither scan hit its cap: [i-back, i+fwd] is the whole run */
+        int rank = 0;
+        for (int t = -back; t <= fwd; t++) {
+          uint64_t o = c[t];
+          rank += (o < k) || (o == k && t < 0);
+        }
+        dst = i - back + rank;
+      } else if (back > 0 && c[-1] > k) {
+        __hip_atomic_store(overflow, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    out_perm[dst] = id[r];
+    if (out_keys) out_keys[dst] = sort_out_word(k, decode_mode);
+  }
+}
+
+/* prefix-plan rule (host): the leading window is the top H active bytes, H
+ * the smallest count whose changed bits reach ceil(log2(n)) + 2; the lower
+ * active bytes are deferred to the tie-fix. Taken only when at least
+ * SORT_PREFIX_MIN_DEFERRED bytes are deferred and the expected number of
+ * same-window partners per row, n * prod_{window bytes} sum_v p_v^2 (byte
+ * independence), is at most 1. Returns the lowest window byte, or -1. */
+#define SORT_PREFIX_MIN_DEFERRED 2
+static int sort_prefix_plan(uint64_t bits_changed, const uint32_t* hghist /* [8][256] */,
+                            int64_t n, int* window_passes, int* deferred_bytes) {
+  int need = 2;
+  while (((int64_t)1 << (need - 2)) < n) need++;
+  int bits = 0, npass = 0, low = -1;
+  for (int b = 7; b >= 0 && bits < need; b--) {
+    unsigned ch = (unsigned)((bits_changed >> (b * 8)) & 0xff);
+    if (!ch) continue;
+    bits += __builtin_popcount(ch);
+    npass++;
+    low = b;
+  }
+  if (bits < need) return -1;
+  int deferred = 0;
+  for (int b = 0; b < low; b++)
+    if ((bits_changed >> (b * 8)) & 0xff) deferred++;
+  if (deferred < SORT_PREFIX_MIN_DEFERRED) return -1;
+  double est = (double)n;
+  for (int b = low; b < 8; b++) {
+    if (!((bits_changed >> (b * 8)) & 0xff)) continue;
+    double s = 0.0;
+    for (int v = 0; v < 256; v++) {
+      double p = (double)hghist[b * 256 + v] / (double)n;
+      s += p * p;
+    }
+    est *= s;
+  }
+  if (est > 1.0) return -1;
+  *window_passes = npass;
+  *deferred_bytes = deferred;
+  return low;
+}
+
+struct sort_plan_rec { int window_passes, deferred_bytes, fell_back; };
+static __thread sort_plan_rec g_sort_plan;
+
+extern "C" void gpuq_sort_last_plan(int* window_passes, int* deferred_bytes,
+                                    int* fell_back) {
+  if (window_passes) *window_passes = g_sort_plan.window_passes;
+  if (deferred_bytes) *deferred_bytes = g_sort_plan.deferred_bytes;
+  if (fell_back) *fell_back = g_sort_plan.fell_back;
+}
+
 /* workspace layout for sort/partition (geometry-aware: the GPUQ_SORT_GEOM
  * env must not change between workspace sizing and the sort call) */
 struct sort_ws {
@@ -1367,7 +1477,7 @@ struct sort_ws {
   uint32_t* ghist;          /* [8][256] global byte histograms */
   uint32_t* gbase;          /* [8][256] per-pass exclusive bin bases */
   unsigned long long* state; /* [nblocks][256] lookback status words */
-  unsigned long long* err;   /* lookback timeout flag */
+  unsigned long long* err;   /* [0] lookback timeout flag, [1] tie-fix overflow */
 };
 
 static int64_t sort_nblocks(int64_t n, int tile) { return (n + tile - 1) / tile; }
@@ -1394,7 +1504,7 @@ static void sort_ws_layout(int64_t n, int nbins, sort_ws* w, char* basep, int64_
   w->ghist = (uint32_t*)take(8 * 256 * 4);
   w->gbase = (uint32_t*)take(8 * 256 * 4);
   w->state = (unsigned long long*)take(nb * 256 * 8);
-  w->err = (unsigned long long*)take(8);
+  w->err = (unsigned long long*)take(16);  /* [0] lookback timeout, [1] tie-fix overflow */
   *total = off;
 }
 
@@ -1432,7 +1542,10 @@ extern "C" int gpuq_sort_perm(void* stream, int64_t n, gpuq_col key,
   scatter_geom geom = get_sort_geom();
   int tile = geom.block * geom.items;
   static __thread int force_classic = 0;
+  static __thread int force_no_prefix = 0;
   bool onesweep = !force_classic && getenv("GPUQ_NO_ONESWEEP") == nullptr;
+  bool no_prefix = force_no_prefix || getenv("GPUQ_SORT_NO_PREFIX") != nullptr;
+  g_sort_plan = sort_plan_rec{0, 0, 0};
 
   /* NULL keys: stable split into [nulls][valids] (or the reverse) per
    * nullOrdering (SortOrder.scala:35-45), then radix-sort the valid subset
@@ -1500,6 +1613,13 @@ extern "C" int gpuq_sort_perm(void* stream, int64_t n, gpuq_col key,
     nibble_mode = false;
   int retries = 0;
 retry:
+  /* prefix plan: radix only the leading window, fix ties in one pass */
+  int prefix_low = -1;
+  if (!nibble_mode && !no_prefix) {
+    int wp = 0, db = 0;
+    prefix_low = sort_prefix_plan(bits_changed, hghist, n_sort, &wp, &db);
+    if (prefix_low >= 0) g_sort_plan = sort_plan_rec{wp, db, 0};
+  }
   if (onesweep && !nibble_mode) {
     /* per-pass exclusive bin bases from the one-read global histograms
      * (replaces the per-pass hist kernel + device scan) */
@@ -1513,7 +1633,7 @@ retry:
     }
     HIP_TRY(hipMemcpyAsync(w.gbase, hgbase, sizeof(hgbase), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(w.state, 0, nb * 256 * 8, s));
-    HIP_TRY(hipMemsetAsync(w.err, 0, 8, s));
+    HIP_TRY(hipMemsetAsync(w.err, 0, 16, s));
   } else if (nibble_mode) {
     /* 16 levels of 4-bit digits (16-bin drains write 16x-longer runs);
      * level bases derived from the same byte histograms */
@@ -1531,7 +1651,9 @@ retry:
     }
     HIP_TRY(hipMemcpyAsync(w.gbase, hgbase, sizeof(hgbase), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(w.state, 0, nb * 256 * 8, s));
-    HIP_TRY(hipMemsetAsync(w.err, 0, 8, s));
+    HIP_TRY(hipMemsetAsync(w.err, 0, 16, s));
+  } else if (prefix_low >= 0) {
+    HIP_TRY(hipMemsetAsync(w.err, 0, 16, s));
   }
 
   /* last active pass writes row ids straight into out_perm (saves the
@@ -1546,13 +1668,17 @@ retry:
   uint32_t *iin = w.ia, *iout = w.ib;
   for (int byte = 0; byte < nlevels; byte++) {
     if (((bits_changed >> (byte * lvl_bits)) & lvl_mask) == 0) continue;  /* RadixSort.java:126 skip */
+    if (byte < prefix_low) continue;  /* deferred to the tie-fix */
     int shift = byte * lvl_bits;
-    uint32_t* iout_pass = (byte == last_byte) ? out_perm + sorted_at : iout;
+    /* under the prefix plan every pass stays in the ping-pong buffers; the
+     * tie-fix writes out_perm and the decoded keys */
+    bool final_pass = byte == last_byte && prefix_low < 0;
+    uint32_t* iout_pass = final_pass ? out_perm + sorted_at : iout;
     /* fuse the key decode into the final pass when the caller wants keys
      * and the null path is not rerouting them through a gather */
     void* dec_out = nullptr;
     int dec_mode = 0;
-    if (byte == last_byte && out_keys && !key.validity) {
+    if (final_pass && out_keys && !key.validity) {
       dec_out = (char*)out_keys;  /* sorted_at == 0 without validity */
       dec_mode = (key.dtype == GPUQ_FLOAT64 ? 2 : 1) | (desc ? 4 : 0);
     }
@@ -1587,12 +1713,43 @@ retry:
     uint32_t* ti = iin; iin = iout_pass; iout = ti;
   }
 
-  if (onesweep) {
+  if (prefix_low >= 0) {
+    void* kdst = (out_keys && !key.validity) ? out_keys : nullptr;
+    int dec_mode = (key.dtype == GPUQ_FLOAT64 ? 2 : 1) | (desc ? 4 : 0);
+    { hipEvent_t _pe = prof_begin(s);
+    k_sort_tiefix<<<dim3((uint32_t)sort_nblocks(n_sort, TIEFIX_TILE)), TIEFIX_BLOCK, 0, s>>>(
+        n_sort, kin, iin, out_perm + sorted_at, (uint64_t*)kdst, prefix_low * 8,
+        dec_mode, &w.err[1]);
+    prof_end("sort_tiefix", s, _pe); }
+    HIP_TRY(hipGetLastError());
+  }
+
+  if (onesweep || prefix_low >= 0) {
     /* one bounded-spin timeout check; on timeout redo with hist+scan (the
-     * input was only read; pass buffers are scratch) */
-    unsigned long long herr = 0;
-    HIP_TRY(hipMemcpyAsync(&herr, w.err, 8, hipMemcpyDeviceToHost, s));
+     * input was only read; pass buffers are scratch). The tie-fix overflow
+     * word rides the same copy. */
+    unsigned long long herr2[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(herr2, w.err, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    unsigned long long herr = onesweep ? herr2[0] : 0;
+    if (!herr && prefix_low >= 0 && herr2[1]) {
+      /* a run longer than GPUQ_SORT_TIE_MAX was not in order: redo with
+       * today's full pass list (same re-encode rules as the timeout path) */
+      g_sort_plan.fell_back = 1;
+      no_prefix = true;
+      if (key.validity) {
+        sort_plan_rec tried = g_sort_plan;
+        force_no_prefix = 1;
+        int rc = gpuq_sort_perm(stream, n, key, desc, nulls_first, out_perm,
+                                out_keys, workspace, workspace_bytes);
+        force_no_prefix = 0;
+        g_sort_plan = tried;
+        return rc;
+      }
+      launch_encode(s, n_sort, key.data, nullptr, key.dtype, desc, &w);
+      HIP_TRY(hipGetLastError());
+      goto retry;
+    }
     if (herr) {
       if (++retries > 1) FAIL(GPUQ_ERR_HIP, "sort: lookback timed out twice");
       onesweep = false;

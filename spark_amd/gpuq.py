@@ -162,6 +162,8 @@ def lib() -> ctypes.CDLL:
                                                   ctypes.c_double, i64, i32,
                                                   vp, vp]
         L.gpuq_range_i64.restype = i32
+        L.gpuq_sort_last_plan.restype = None
+        L.gpuq_sort_last_plan.argtypes = [ctypes.POINTER(ctypes.c_int)] * 3
         L.gpuq_range_i64.argtypes = [vp, i64, i64, i64, vp]
         L.gpuq_cast_i64_f64.restype = i32
         L.gpuq_cast_i64_f64.argtypes = [vp, i64, vp, vp]
@@ -249,6 +251,14 @@ def sort_perm(keys: torch.Tensor, desc=False, nulls_first=None, workspace=None,
                                 perm.data_ptr(), _dp(ok),
                                 workspace.data_ptr(), workspace.numel()))
     return perm, ok
+
+
+def sort_last_plan():
+    """(window_passes, deferred_bytes, fell_back) of the last sort_perm on this
+    thread; deferred_bytes == 0 means the classic all-active-bytes plan ran."""
+    wp, db, fb = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    lib().gpuq_sort_last_plan(ctypes.byref(wp), ctypes.byref(db), ctypes.byref(fb))
+    return wp.value, db.value, fb.value
 
 
 def gather(col: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
