@@ -100,7 +100,13 @@ int64_t gpuq_sort_workspace_bytes(int64_t nrows);
  * input) to out_perm[nrows] (uint32) and, if out_keys != NULL, the sorted
  * key column. With key.validity set, NULL rows are placed per nulls_first
  * in input order and out_keys carries the input's raw values at those
- * positions (callers track NULL-ness via the permuted validity). */
+ * positions (callers track NULL-ness via the permuted validity).
+ * The key column is read more than once during the call (a histogram
+ * pre-pass, then the first radix pass, and again if the sort redoes itself),
+ * so it must not change until the work this call put on the stream has
+ * finished; it is never written. An
+ * out_keys that overlaps the key column is allowed: it selects the path that
+ * first materialises an encoded copy of the keys in the workspace. */
 int gpuq_sort_perm(void* stream, int64_t nrows, gpuq_col key,
                    int32_t desc, int32_t nulls_first,
                    uint32_t* out_perm, void* out_keys,

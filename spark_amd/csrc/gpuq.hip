@@ -179,6 +179,17 @@ DEV uint64_t sort_out_word(uint64_t kk, int decode_mode) {
   return e ^ SIGNBIT;
 }
 
+/* sort input word for a raw key: the inverse direction of sort_out_word.
+ * in_mode 0 = the word is already encoded, 1 = int64, 2 = float64 (-0.0 ->
+ * +0.0, canonical NaN: encode_f64), +4 = complement for DESC. Used by the
+ * fused first scatter pass, which reads the caller's column directly. */
+DEV uint64_t sort_in_word(uint64_t raw, int in_mode) {
+  if (!in_mode) return raw;
+  uint64_t e = (in_mode & 2) ? encode_f64(__longlong_as_double((long long)raw))
+                             : encode_i64((int64_t)raw);
+  return (in_mode & 4) ? ~e : e;
+}
+
 DEV bool bit_valid(const uint8_t* validity, int64_t i) {
   return !validity || ((validity[i >> 3] >> (i & 7)) & 1);
 }
@@ -441,7 +452,13 @@ extern "C" int gpuq_gather(void* stream, int64_t n, gpuq_col col,
 /* encode + identity rowids + skip-byte AND/OR reduction + ALL EIGHT global
  * byte histograms in one read (one pass replaces the reference's per-byte
  * count loops, RadixSort.java:126-135; per-byte histograms are invariant
- * under the passes' permutations, so one upfront count serves every pass). */
+ * under the passes' permutations, so one upfront count serves every pass).
+ * Histogram-only mode (ek == idx == nullptr, no rowmap): the reduction and
+ * the histograms over keys encoded in registers, nothing materialised — the
+ * pre-pass of the fused first scatter pass. Four keys per thread are in
+ * flight per iteration there (measured against one key per thread, wave-
+ * private and lane-interleaved histogram copies and contiguous tiles:
+ * profiles/README.md, "Fused first pass"). */
 template <int DTYPE, bool DESC>
 __global__ void k_encode(int64_t n, const void* keys, const uint32_t* rowmap,
                          uint64_t* ek, uint32_t* idx,
@@ -453,14 +470,33 @@ __global__ void k_encode(int64_t n, const void* keys, const uint32_t* rowmap,
   uint64_t acc_or = 0, acc_and = ~0ULL;
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (!ek) {
+    for (; i + 3 * stride < n; i += 4 * stride) {
+      uint64_t e[4];
+      #pragma unroll
+      for (int u = 0; u < 4; u++) {
+        if (DTYPE == GPUQ_FLOAT64) e[u] = encode_f64(((const double*)keys)[i + u * stride]);
+        else e[u] = encode_i64(((const int64_t*)keys)[i + u * stride]);
+        if (DESC) e[u] = ~e[u];
+      }
+      #pragma unroll
+      for (int u = 0; u < 4; u++) {
+        acc_or |= e[u]; acc_and &= e[u];
+        #pragma unroll
+        for (int b = 0; b < 8; b++) atomicAdd(&h[b][(e[u] >> (b * 8)) & 0xff], 1u);
+      }
+    }
+  }
   for (; i < n; i += stride) {
     uint64_t e;
     uint32_t row = rowmap ? rowmap[i] : (uint32_t)i;
     if (DTYPE == GPUQ_FLOAT64) e = encode_f64(((const double*)keys)[row]);
     else e = encode_i64(((const int64_t*)keys)[row]);
     if (DESC) e = ~e;
-    ek[i] = e;
-    idx[i] = row;
+    if (ek) {
+      ek[i] = e;
+      idx[i] = row;
+    }
     acc_or |= e; acc_and &= e;
     #pragma unroll
     for (int b = 0; b < 8; b++) atomicAdd(&h[b][(e >> (b * 8)) & 0xff], 1u);
@@ -655,7 +691,10 @@ void k_radix_scatter(int64_t n, const uint64_t* kin, const PayT* iin,
                      unsigned long long* err_flag, uint32_t epoch,
                      void* decode_out /* non-null on the final pass: write
                        decoded keys here instead of encoded keys to kout */,
-                     int decode_mode /* 1=i64 2=f64, +4 = desc */) {
+                     int decode_mode /* 1=i64 2=f64, +4 = desc */,
+                     int in_mode /* non-zero on a fused first pass: kin is the
+                       caller's raw column (1=i64 2=f64, +4 = desc), encoded
+                       in registers; iin == nullptr then means id = row index */) {
   constexpr int WAVES = BLOCK / WAVE;
   constexpr int TILE = BLOCK * ITEMS;
   constexpr int BINS = 1 << RADIX_BITS;
@@ -688,12 +727,28 @@ void k_radix_scatter(int64_t n, const uint64_t* kin, const PayT* iin,
   const int64_t wbase = base + (int64_t)wave * WAVE * ITEMS;
   /* issue every load before the serial ranking chain so all ITEMS pairs
    * are in flight at once (A/B via GPUQ_SCATTER_NO_PRELOAD) */
-  #pragma unroll
-  for (int r = 0; r < ITEMS; r++) {
-    int64_t i = wbase + r * WAVE + lane;
-    bool valid = i < n;
-    k[r] = valid ? kin[i] : 0;
-    id[r] = valid ? iin[i] : 0;
+  if (iin) {
+    #pragma unroll
+    for (int r = 0; r < ITEMS; r++) {
+      int64_t i = wbase + r * WAVE + lane;
+      bool valid = i < n;
+      k[r] = valid ? kin[i] : 0;
+      id[r] = valid ? iin[i] : 0;
+    }
+  } else {
+    /* fused first pass: one 8-byte load per lane (the column may start at
+     * any 8-byte offset), the row id is the row's index */
+    #pragma unroll
+    for (int r = 0; r < ITEMS; r++) {
+      int64_t i = wbase + r * WAVE + lane;
+      k[r] = i < n ? kin[i] : 0;
+      id[r] = (PayT)i;
+    }
+  }
+  if (in_mode) {
+    /* rows past n get a meaningless word here; they are never binned or staged */
+    #pragma unroll
+    for (int r = 0; r < ITEMS; r++) k[r] = sort_in_word(k[r], in_mode);
   }
   for (int r = 0; r < ITEMS; r++) {
     int64_t i = wbase + r * WAVE + lane;
@@ -989,40 +1044,41 @@ static void launch_scatter(hipStream_t s, scatter_geom g, int64_t nb,
                            const uint32_t* scanned, int shift, int nparts,
                            unsigned long long* state, const uint32_t* gbase,
                            unsigned long long* err_flag, uint32_t epoch,
-                           void* decode_out = nullptr, int decode_mode = 0) {
+                           void* decode_out = nullptr, int decode_mode = 0,
+                           int in_mode = 0) {
   dim3 grid((uint32_t)nb);
 #define LS(B, I) k_radix_scatter<BIN_MODE, B, I, LOOKBACK><<<grid, B, 0, s>>>( \
       n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase, \
-      err_flag, epoch, decode_out, decode_mode)
+      err_flag, epoch, decode_out, decode_mode, in_mode)
   static int contig = -1;
   if (contig < 0) contig = getenv("GPUQ_DRAIN_CONTIG") != nullptr;
   if (contig && g.block == 512 && (g.items == 9 || g.items == 10 || g.items == 11)) {
     if (g.items == 9)
       k_radix_scatter<BIN_MODE, 512, 9, LOOKBACK, uint32_t, 8, true><<<grid, 512, 0, s>>>(
           n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-          err_flag, epoch, decode_out, decode_mode);
+          err_flag, epoch, decode_out, decode_mode, in_mode);
     else if (g.items == 11)
       k_radix_scatter<BIN_MODE, 512, 11, LOOKBACK, uint32_t, 8, true><<<grid, 512, 0, s>>>(
           n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-          err_flag, epoch, decode_out, decode_mode);
+          err_flag, epoch, decode_out, decode_mode, in_mode);
     else
       k_radix_scatter<BIN_MODE, 512, 10, LOOKBACK, uint32_t, 8, true><<<grid, 512, 0, s>>>(
           n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-          err_flag, epoch, decode_out, decode_mode);
+          err_flag, epoch, decode_out, decode_mode, in_mode);
     return;
   }
   if (g.block == 256 && g.items == 20)
     k_radix_scatter<BIN_MODE, 256, 20, LOOKBACK><<<grid, 256, 0, s>>>(
       n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-      err_flag, epoch, decode_out, decode_mode);
+      err_flag, epoch, decode_out, decode_mode, in_mode);
   else if (g.block == 256 && g.items == 22)
     k_radix_scatter<BIN_MODE, 256, 22, LOOKBACK><<<grid, 256, 0, s>>>(
       n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-      err_flag, epoch, decode_out, decode_mode);
+      err_flag, epoch, decode_out, decode_mode, in_mode);
   else if (g.block == 512 && g.items == 11)
     k_radix_scatter<BIN_MODE, 512, 11, LOOKBACK><<<grid, 512, 0, s>>>(
       n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-      err_flag, epoch, decode_out, decode_mode);
+      err_flag, epoch, decode_out, decode_mode, in_mode);
   else if (g.block == 256 && g.items == 16) LS(256, 16);
   else if (g.block == 512 && g.items == 8) LS(512, 8);
   else if (g.block == 512 && g.items == 16) LS(512, 16);
@@ -1031,23 +1087,23 @@ static void launch_scatter(hipStream_t s, scatter_geom g, int64_t nb,
   else if (g.block == 512 && g.items == 6)
     k_radix_scatter<BIN_MODE, 512, 6, LOOKBACK><<<grid, 512, 0, s>>>(
       n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-      err_flag, epoch, decode_out, decode_mode);
+      err_flag, epoch, decode_out, decode_mode, in_mode);
   else if (g.block == 256 && g.items == 12)
     k_radix_scatter<BIN_MODE, 256, 12, LOOKBACK><<<grid, 256, 0, s>>>(
       n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-      err_flag, epoch, decode_out, decode_mode);
+      err_flag, epoch, decode_out, decode_mode, in_mode);
   else if (g.block == 512 && g.items == 12)
     k_radix_scatter<BIN_MODE, 512, 12, LOOKBACK><<<grid, 512, 0, s>>>(
       n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-      err_flag, epoch, decode_out, decode_mode);
+      err_flag, epoch, decode_out, decode_mode, in_mode);
   else if (g.block == 1024 && g.items == 5)
     k_radix_scatter<BIN_MODE, 1024, 5, LOOKBACK><<<grid, 1024, 0, s>>>(
       n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-      err_flag, epoch, decode_out, decode_mode);
+      err_flag, epoch, decode_out, decode_mode, in_mode);
   else if (g.block == 512 && g.items == 10)
     k_radix_scatter<BIN_MODE, 512, 10, LOOKBACK><<<grid, 512, 0, s>>>(
       n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-      err_flag, epoch, decode_out, decode_mode);
+      err_flag, epoch, decode_out, decode_mode, in_mode);
   else if (g.block == 1024 && g.items == 2) LS(1024, 2);
   else if (g.block == 1024 && g.items == 6) LS(1024, 6);
   else LS(1024, 4);
@@ -1320,19 +1376,19 @@ static void launch_scatter4(hipStream_t s, scatter_geom g, int64_t nb,
   if (g.block == 1024 && g.items == 8)
     k_radix_scatter<BIN_MODE, 1024, 8, LOOKBACK, uint32_t, 4><<<grid, 1024, 0, s>>>(
         n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-        err_flag, epoch, decode_out, decode_mode);
+        err_flag, epoch, decode_out, decode_mode, 0 /* in_mode: never fused */);
   else if (g.block == 256 && g.items == 22)
     k_radix_scatter<BIN_MODE, 256, 22, LOOKBACK, uint32_t, 4><<<grid, 256, 0, s>>>(
         n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-        err_flag, epoch, decode_out, decode_mode);
+        err_flag, epoch, decode_out, decode_mode, 0 /* in_mode: never fused */);
   else if (g.block == 512 && g.items == 10)
     k_radix_scatter<BIN_MODE, 512, 10, LOOKBACK, uint32_t, 4><<<grid, 512, 0, s>>>(
         n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-        err_flag, epoch, decode_out, decode_mode);
+        err_flag, epoch, decode_out, decode_mode, 0 /* in_mode: never fused */);
   else
     k_radix_scatter<BIN_MODE, 512, 10, LOOKBACK, uint32_t, 4><<<grid, 512, 0, s>>>(
         n, kin, iin, kout, iout, scanned, shift, (int)nb, nparts, state, gbase,
-        err_flag, epoch, decode_out, decode_mode);  /* unreachable: gated above */
+        err_flag, epoch, decode_out, decode_mode, 0 /* in_mode: never fused */);  /* unreachable: gated above */
 }
 
 /* decode sorted keys back to the output dtype */
@@ -1514,14 +1570,19 @@ extern "C" int64_t gpuq_sort_workspace_bytes(int64_t n) {
   return total;
 }
 
+/* hist_only: the pre-pass of the fused first scatter pass — reduction and
+ * histograms only, w->ka / w->ia stay unwritten (no rowmap in that mode) */
 static void launch_encode(hipStream_t s, int64_t n, const void* keys,
-                          const uint32_t* rowmap, int dtype, int desc, sort_ws* w) {
+                          const uint32_t* rowmap, int dtype, int desc, sort_ws* w,
+                          bool hist_only = false) {
+  uint64_t* ek = hist_only ? nullptr : w->ka;
+  uint32_t* idx = hist_only ? nullptr : w->ia;
   if (dtype == GPUQ_FLOAT64) {
-    if (desc) k_encode<GPUQ_FLOAT64, true><<<grid1d(n), 256, 0, s>>>(n, keys, rowmap, w->ka, w->ia, &w->bits[0], &w->bits[1], w->ghist);
-    else      k_encode<GPUQ_FLOAT64, false><<<grid1d(n), 256, 0, s>>>(n, keys, rowmap, w->ka, w->ia, &w->bits[0], &w->bits[1], w->ghist);
+    if (desc) k_encode<GPUQ_FLOAT64, true><<<grid1d(n), 256, 0, s>>>(n, keys, rowmap, ek, idx, &w->bits[0], &w->bits[1], w->ghist);
+    else      k_encode<GPUQ_FLOAT64, false><<<grid1d(n), 256, 0, s>>>(n, keys, rowmap, ek, idx, &w->bits[0], &w->bits[1], w->ghist);
   } else {
-    if (desc) k_encode<GPUQ_INT64, true><<<grid1d(n), 256, 0, s>>>(n, keys, rowmap, w->ka, w->ia, &w->bits[0], &w->bits[1], w->ghist);
-    else      k_encode<GPUQ_INT64, false><<<grid1d(n), 256, 0, s>>>(n, keys, rowmap, w->ka, w->ia, &w->bits[0], &w->bits[1], w->ghist);
+    if (desc) k_encode<GPUQ_INT64, true><<<grid1d(n), 256, 0, s>>>(n, keys, rowmap, ek, idx, &w->bits[0], &w->bits[1], w->ghist);
+    else      k_encode<GPUQ_INT64, false><<<grid1d(n), 256, 0, s>>>(n, keys, rowmap, ek, idx, &w->bits[0], &w->bits[1], w->ghist);
   }
 }
 
@@ -1591,18 +1652,6 @@ extern "C" int gpuq_sort_perm(void* stream, int64_t n, gpuq_col key,
   HIP_TRY(hipMemsetAsync(w.bits, 0, 16, s));
   HIP_TRY(hipMemsetAsync(w.bits, 0xFF, 8, s));  /* bits_and = ~0 */
   HIP_TRY(hipMemsetAsync(w.ghist, 0, 8 * 256 * 4, s));
-  /* encode + skip-byte reduction + all-byte global histograms (one read) */
-  { hipEvent_t _pe = prof_begin(s);
-  launch_encode(s, n_sort, key.data, rowmap, key.dtype, desc, &w);
-  prof_end("encode", s, _pe); }
-  HIP_TRY(hipGetLastError());
-  unsigned long long hb[2];
-  uint32_t hghist[8 * 256];
-  HIP_TRY(hipMemcpyAsync(hb, w.bits, 16, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(hghist, w.ghist, sizeof(hghist), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  uint64_t bits_changed = hb[0] ^ hb[1];
-
   bool nibble_mode = onesweep && getenv("GPUQ_SORT_BITS") != nullptr &&
                      atoi(getenv("GPUQ_SORT_BITS")) == 4;
   /* the 4-bit kernel templates exist for these geometries only; a tile
@@ -1611,6 +1660,40 @@ extern "C" int gpuq_sort_perm(void* stream, int64_t n, gpuq_col key,
                        (geom.block == 512 && geom.items == 10) ||
                        (geom.block == 256 && geom.items == 22)))
     nibble_mode = false;
+  /* fused first pass: the first scatter pass reads the caller's column and
+   * encodes in registers, so only the reduction and the histograms are
+   * needed up front (k_encode in histogram-only mode). The column is then
+   * read again by that pass and by a redo, and the final pass may write
+   * out_keys while the column is still being read: an out_keys that overlaps
+   * it takes the materialising path. */
+  const char* kraw = (const char*)key.data;
+  bool keys_alias = out_keys && (const char*)out_keys < kraw + n * 8 &&
+                    kraw < (const char*)out_keys + n * 8;
+  bool fused = onesweep && !nibble_mode && !key.validity && !keys_alias &&
+               getenv("GPUQ_SORT_NO_FUSED_ENCODE") == nullptr;
+  const int key_mode = (key.dtype == GPUQ_FLOAT64 ? 2 : 1) | (desc ? 4 : 0);
+  /* encode + skip-byte reduction + all-byte global histograms (one read) */
+  { hipEvent_t _pe = prof_begin(s);
+  launch_encode(s, n_sort, key.data, rowmap, key.dtype, desc, &w, fused);
+  prof_end(fused ? "sort_hist" : "encode", s, _pe); }
+  HIP_TRY(hipGetLastError());
+  unsigned long long hb[2];
+  uint32_t hghist[8 * 256];
+  HIP_TRY(hipMemcpyAsync(hb, w.bits, 16, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(hghist, w.ghist, sizeof(hghist), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  uint64_t bits_changed = hb[0] ^ hb[1];
+  if (fused && bits_changed == 0) {
+    /* all keys equal: no pass runs, and the zero-pass tail below copies the
+     * identity row ids and decodes the keys from w.ia / w.ka — materialise
+     * them. (The device-side ghist counts twice after this; only the host
+     * copy above is used from here on.) */
+    fused = false;
+    { hipEvent_t _pe = prof_begin(s);
+    launch_encode(s, n_sort, key.data, nullptr, key.dtype, desc, &w);
+    prof_end("encode", s, _pe); }
+    HIP_TRY(hipGetLastError());
+  }
   int retries = 0;
 retry:
   /* prefix plan: radix only the leading window, fix ties in one pass */
@@ -1664,8 +1747,14 @@ retry:
   int last_byte = -1;
   for (int lvl = 0; lvl < nlevels; lvl++)
     if (((bits_changed >> (lvl * lvl_bits)) & lvl_mask) != 0) last_byte = lvl;
-  uint64_t *kin = w.ka, *kout = w.kb;
-  uint32_t *iin = w.ia, *iout = w.ib;
+  /* pass input: the ping-pong scratch, or on the fused first pass the
+   * caller's column (read-only: it never enters kout/knext, the two buffers
+   * the passes write) with row ids synthesised from the row index */
+  const uint64_t* kin = fused ? (const uint64_t*)key.data : w.ka;
+  const uint32_t* iin = fused ? nullptr : w.ia;
+  uint64_t *kout = w.kb, *knext = w.ka;
+  uint32_t *iout = w.ib, *inext = w.ia;
+  int in_mode = fused ? key_mode : 0;   /* cleared after the first active pass */
   for (int byte = 0; byte < nlevels; byte++) {
     if (((bits_changed >> (byte * lvl_bits)) & lvl_mask) == 0) continue;  /* RadixSort.java:126 skip */
     if (byte < prefix_low) continue;  /* deferred to the tie-fix */
@@ -1693,7 +1782,7 @@ retry:
       { hipEvent_t _pe = prof_begin(s);
       launch_scatter<0, true>(s, geom, nb, n_sort, kin, iin, kout, iout_pass, nullptr,
                               shift, 0, w.state, w.gbase + byte * 256, w.err,
-                              (uint32_t)(byte + 1), dec_out, dec_mode);
+                              (uint32_t)(byte + 1), dec_out, dec_mode, in_mode);
       prof_end("radix_scatter", s, _pe); }
       HIP_TRY(hipGetLastError());
     } else {
@@ -1709,8 +1798,11 @@ retry:
       prof_end("radix_scatter", s, _pe); }
       HIP_TRY(hipGetLastError());
     }
-    uint64_t* tk = kin; kin = kout; kout = tk;
-    uint32_t* ti = iin; iin = iout_pass; iout = ti;
+    /* the buffers just written become the input; the other scratch pair
+     * becomes the output (a fused first pass's input drops out here) */
+    uint64_t* kdone = kout; kout = knext; knext = kdone; kin = kdone;
+    uint32_t* idone = iout; iout = inext; inext = idone; iin = iout_pass;
+    in_mode = 0;
   }
 
   if (prefix_low >= 0) {
@@ -1746,8 +1838,12 @@ retry:
         g_sort_plan = tried;
         return rc;
       }
-      launch_encode(s, n_sort, key.data, nullptr, key.dtype, desc, &w);
-      HIP_TRY(hipGetLastError());
+      /* fused: the raw column is intact and the redo's first pass reads it
+       * again; otherwise ka/ia were consumed as scratch — re-encode */
+      if (!fused) {
+        launch_encode(s, n_sort, key.data, nullptr, key.dtype, desc, &w);
+        HIP_TRY(hipGetLastError());
+      }
       goto retry;
     }
     if (herr) {
@@ -1763,6 +1859,9 @@ retry:
         force_classic = 0;
         return rc;
       }
+      /* hist+scan is unfused: materialise the pairs (also when the timed-out
+       * attempt was fused and never wrote ka/ia) */
+      fused = false;
       launch_encode(s, n_sort, key.data, nullptr, key.dtype, desc, &w);
       HIP_TRY(hipGetLastError());
       goto retry;
