@@ -125,6 +125,48 @@ int gpuq_sort_perm(void* stream, int64_t nrows, gpuq_col key,
  * Any pointer may be NULL. */
 void gpuq_sort_last_plan(int* window_passes, int* deferred_bytes, int* fell_back);
 
+/* ---------------------------------------------------------------- */
+/* TOP-K — the selection under TakeOrderedAndProjectExec             */
+/* (execution/limit.scala): the rows of the first k positions of the */
+/* sort order, found by an MSB radix select over the sort's own key  */
+/* encodings instead of a full sort. Let S be the stable order       */
+/* gpuq_sort_perm(key, desc, nulls_first) produces (float64: -0.0 == */
+/* 0.0, all NaNs equal and greatest; NULLs one group, first or last  */
+/* per nulls_first) and T the group of rows equal in that order that */
+/* holds position min(k, nrows) - 1 of S. T may be the NULL group.   */
+/* ---------------------------------------------------------------- */
+
+/* workspace bytes for gpuq_topk_candidates at nrows; pure arithmetic */
+int64_t gpuq_topk_workspace_bytes(int64_t nrows);
+
+/* Writes the candidate row ids to out_rids in ASCENDING row-id (input)
+ * order, so a stable sort of the gathered candidates reproduces the head of
+ * S exactly, and sets out_counts = {n_cand, n_before, n_tie} (HOST int64[3]):
+ * n_before rows sort strictly before T, n_tie = |T|.
+ *  - keep_ties == 0: the n_before rows before T plus the first
+ *    min(k, nrows) - n_before rows of T in input order, so n_cand ==
+ *    min(k, nrows) and the candidates are exactly the rows of S[:k].
+ *  - keep_ties == 1: the rows before T plus all of T, n_cand == n_before +
+ *    n_tie (for callers whose further sort keys break the tie).
+ * out_counts is always set. If n_cand > out_capacity nothing is written and
+ * GPUQ_ERR_OVERFLOW is returned (call again with n_cand entries), the
+ * convention of gpuq_join_probe_keys; the counts are known on the host
+ * before the emit kernels are launched. k <= 0 or nrows == 0 gives {0,0,0}
+ * and GPUQ_OK with nothing launched. nrows > 0xFFFFFFFF, a dtype other than
+ * int64/float64 or a short workspace return GPUQ_ERR_INVALID before anything
+ * is launched.
+ * The key column (and its validity bitmap) is read several times during the
+ * call — once per select level until the surviving bucket has been copied to
+ * the workspace, then twice by the emit — with host synchronisations in
+ * between, so it must not change until the call returns; it is never
+ * written. */
+int gpuq_topk_candidates(void* stream, int64_t nrows, gpuq_col key,
+                         int32_t desc, int32_t nulls_first, int64_t k,
+                         int32_t keep_ties,
+                         uint32_t* out_rids, int64_t out_capacity,
+                         int64_t* out_counts /* HOST int64[3] */,
+                         void* workspace, int64_t workspace_bytes);
+
 /* out[i] = col[perm[i]] — payload materialization after sort/partition. */
 int gpuq_gather(void* stream, int64_t nrows, gpuq_col col,
                 const uint32_t* perm, void* out);

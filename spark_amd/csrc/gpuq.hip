@@ -1892,6 +1892,441 @@ retry:
   return GPUQ_OK;
 }
 
+/* ================= top-k (radix select) ================= */
+/*
+ * TakeOrderedAndProjectExec (execution/limit.scala) keeps the first k rows of
+ * a sort order. Instead of sorting everything, an MSB radix select finds the
+ * k-th key of the sort's own encoding (sort_in_word), then one stable stream
+ * compaction emits the rows before it plus the boundary ties.
+ *
+ *  level   k_topk_hist: 256-bin histogram of one key byte over the rows whose
+ *          higher bytes equal the prefix fixed so far. The host copies the
+ *          256 counts, picks the digit that holds the remaining rank and
+ *          moves to the next active byte (bytes uniform over the column are
+ *          skipped by the sort's bits_changed rule; the first level produces
+ *          that reduction and the NULL count).
+ *  collect k_topk_collect: once the surviving bucket has at most
+ *          TOPK_COMPACT_MAX rows, the same streaming read also appends the
+ *          bucket's encoded keys to a workspace buffer; later levels read
+ *          that buffer instead of the column.
+ *  emit    k_topk_count + exclusive_scan_u32 + k_topk_emit: per-block counts
+ *          of (before, tie) rows, their prefix sums, then a ranked write of
+ *          the selected row ids in input order.
+ */
+
+#define TOPK_COMPACT_MAX (1 << 20)
+#define TOPK_BLOCK 256
+#define TOPK_WAVES (TOPK_BLOCK / WAVE)
+#define TOPK_EMIT_ITEMS 8
+#define TOPK_EMIT_TILE (TOPK_BLOCK * TOPK_EMIT_ITEMS) /* 2048 rows per block */
+
+/* row classes of the emit: before the tie group T, in T, after T */
+#define TOPK_BEFORE 0
+#define TOPK_TIE 1
+#define TOPK_AFTER 2
+
+/* one LDS histogram increment per calling lane. When every calling lane of
+ * the wave hits the same bin (a byte that is almost uniform, such as the
+ * exponent byte of unit-range doubles) one lane adds the lane count instead
+ * of 64 serialised same-address atomics. */
+DEV void topk_hist_add(uint32_t* h, int bin) {
+  unsigned long long act = __ballot(1);
+  int b0 = __builtin_amdgcn_readfirstlane(bin);
+  unsigned long long same = __ballot(bin == b0);
+  if (same == act) {
+    if ((int)__lane_id() == __ffsll((long long)act) - 1)
+      atomicAdd(&h[b0], (uint32_t)__popcll(act));
+  } else {
+    atomicAdd(&h[bin], 1u);
+  }
+}
+
+/* One select level. src holds raw keys (key_mode per sort_in_word) with an
+ * optional validity bitmap, or the collected encoded keys (key_mode 0, no
+ * bitmap). Counts byte `shift/8` of every valid row with
+ * ((e ^ prefix) & mask) == 0 into ghist[256] (one global atomic per block
+ * and non-zero bin). stats != nullptr (first level): also the AND / OR
+ * reduction over the valid rows and the NULL count, stats = {and, or, nnull}.
+ * Four keys per thread are in flight per iteration, as in k_encode. */
+__global__ __launch_bounds__(TOPK_BLOCK)
+void k_topk_hist(int64_t n, const uint64_t* src, const uint8_t* validity,
+                 int key_mode, uint64_t prefix, uint64_t mask, int shift,
+                 uint32_t* ghist, unsigned long long* stats) {
+  __shared__ uint32_t h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  uint64_t acc_or = 0, acc_and = ~0ULL;
+  uint32_t nulls = 0;
+  int64_t i = (int64_t)blockIdx.x * TOPK_BLOCK + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * TOPK_BLOCK;
+  for (; i + 3 * stride < n; i += 4 * stride) {
+    uint64_t raw[4];
+    bool ok[4];
+    #pragma unroll
+    for (int u = 0; u < 4; u++) {
+      raw[u] = src[i + u * stride];
+      ok[u] = bit_valid(validity, i + u * stride);
+    }
+    #pragma unroll
+    for (int u = 0; u < 4; u++) {
+      if (!ok[u]) { nulls++; continue; }
+      uint64_t e = sort_in_word(raw[u], key_mode);
+      acc_or |= e; acc_and &= e;
+      if (((e ^ prefix) & mask) == 0) topk_hist_add(h, (int)((e >> shift) & 0xff));
+    }
+  }
+  for (; i < n; i += stride) {
+    if (!bit_valid(validity, i)) { nulls++; continue; }
+    uint64_t e = sort_in_word(src[i], key_mode);
+    acc_or |= e; acc_and &= e;
+    if (((e ^ prefix) & mask) == 0) topk_hist_add(h, (int)((e >> shift) & 0xff));
+  }
+  if (stats) {
+    /* wave reduce then one atomic per wave (G12) */
+    for (int off = 32; off > 0; off >>= 1) {
+      acc_or |= __shfl_down((unsigned long long)acc_or, off);
+      acc_and &= __shfl_down((unsigned long long)acc_and, off);
+      nulls += __shfl_down(nulls, off);
+    }
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+      atomicAnd(&stats[0], (unsigned long long)acc_and);
+      atomicOr(&stats[1], (unsigned long long)acc_or);
+      if (nulls) atomicAdd(&stats[2], (unsigned long long)nulls);
+    }
+  }
+  __syncthreads();
+  uint32_t v = h[threadIdx.x];
+  if (v) atomicAdd(&ghist[threadIdx.x], v);
+}
+
+/* Bucket compaction fused with the next level: every valid row of the column
+ * with ((e ^ prefix) & mask) == 0 is appended (encoded) to cbuf — order is
+ * irrelevant to a histogram — and counted into ghist by byte `shift/8`.
+ * A block walks tiles of TOPK_COLLECT_TILE consecutive rows, stages its
+ * matches in LDS (one LDS bump per wave) and flushes the stage with ONE bump
+ * of the global cursor and coalesced stores whenever another tile might not
+ * fit, so the cursor sees one returning atomic per ~1-2 K collected rows, not
+ * one per wave. cap is the bucket size the previous level counted; the bound
+ * on the write only matters if the caller broke the contract and changed the
+ * column meanwhile. */
+#define TOPK_COLLECT_ITEMS 4
+#define TOPK_COLLECT_TILE (TOPK_BLOCK * TOPK_COLLECT_ITEMS) /* 1024 */
+#define TOPK_STAGE (2 * TOPK_COLLECT_TILE)
+
+__global__ __launch_bounds__(TOPK_BLOCK)
+void k_topk_collect(int64_t n, const uint64_t* src, const uint8_t* validity,
+                    int key_mode, uint64_t prefix, uint64_t mask, int shift,
+                    uint32_t* ghist, uint64_t* cbuf, unsigned int* cursor,
+                    uint32_t cap) {
+  __shared__ uint32_t h[256];
+  __shared__ uint64_t stage[TOPK_STAGE];
+  __shared__ uint32_t staged, gbase;
+  h[threadIdx.x] = 0;
+  if (threadIdx.x == 0) staged = 0;
+  __syncthreads();
+  const unsigned long long lt = (1ULL << __lane_id()) - 1;
+  /* called by the whole block, after a barrier that follows the last add */
+  auto flush = [&]() {
+    if (threadIdx.x == 0) gbase = staged ? atomicAdd(cursor, staged) : 0;
+    __syncthreads();
+    uint32_t cnt = staged, gb = gbase;
+    for (uint32_t j = threadIdx.x; j < cnt; j += TOPK_BLOCK)
+      if (gb + j < cap) cbuf[gb + j] = stage[j];
+    __syncthreads();
+    if (threadIdx.x == 0) staged = 0;
+    __syncthreads();
+  };
+  /* the trip count depends on blockIdx only: every barrier below is uniform */
+  for (int64_t base = (int64_t)blockIdx.x * TOPK_COLLECT_TILE; base < n;
+       base += (int64_t)gridDim.x * TOPK_COLLECT_TILE) {
+    uint64_t raw[TOPK_COLLECT_ITEMS];
+    bool ok[TOPK_COLLECT_ITEMS];
+    #pragma unroll
+    for (int u = 0; u < TOPK_COLLECT_ITEMS; u++) {
+      int64_t i = base + u * TOPK_BLOCK + threadIdx.x;
+      ok[u] = i < n && bit_valid(validity, i);
+      raw[u] = i < n ? src[i] : 0;
+    }
+    #pragma unroll
+    for (int u = 0; u < TOPK_COLLECT_ITEMS; u++) {
+      uint64_t e = sort_in_word(raw[u], key_mode);
+      if (ok[u] && ((e ^ prefix) & mask) == 0) {
+        unsigned long long act = __ballot(1);
+        uint32_t rank = (uint32_t)__popcll(act & lt);
+        uint32_t slot = 0;
+        if (rank == 0) slot = atomicAdd(&staged, (uint32_t)__popcll(act));
+        slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot) + rank;
+        stage[slot] = e;   /* < TOPK_STAGE: at most one tile since the last check */
+        topk_hist_add(h, (int)((e >> shift) & 0xff));
+      }
+    }
+    __syncthreads();
+    uint32_t have = staged;
+    __syncthreads();   /* nobody adds again before everyone has read `have` */
+    if (have > TOPK_STAGE - TOPK_COLLECT_TILE) flush();
+  }
+  flush();
+  uint32_t v = h[threadIdx.x];
+  if (v) atomicAdd(&ghist[threadIdx.x], v);
+}
+
+/* class of row i against the threshold: NULL rows take null_class; valid rows
+ * take valid_class when it is >= 0 (T is the NULL group), else compare. */
+DEV int topk_class(const uint64_t* keys, const uint8_t* validity, int64_t i,
+                   int key_mode, uint64_t thr, int null_class, int valid_class) {
+  uint64_t e = sort_in_word(keys[i], key_mode);
+  if (!bit_valid(validity, i)) return null_class;
+  if (valid_class >= 0) return valid_class;
+  return e < thr ? TOPK_BEFORE : (e == thr ? TOPK_TIE : TOPK_AFTER);
+}
+
+/* emit phase 1: block b counts the before / tie rows of its tile of
+ * TOPK_EMIT_TILE consecutive rows into cnt[b] / cnt[nblocks + b]. */
+__global__ __launch_bounds__(TOPK_BLOCK)
+void k_topk_count(int64_t n, const uint64_t* keys, const uint8_t* validity,
+                  int key_mode, uint64_t thr, int null_class, int valid_class,
+                  uint32_t* cnt, uint32_t nblocks) {
+  __shared__ uint32_t c[2];
+  if (threadIdx.x < 2) c[threadIdx.x] = 0;
+  __syncthreads();
+  int64_t base = (int64_t)blockIdx.x * TOPK_EMIT_TILE;
+  uint32_t nb = 0, nt = 0;
+  #pragma unroll
+  for (int r = 0; r < TOPK_EMIT_ITEMS; r++) {
+    int64_t i = base + r * TOPK_BLOCK + threadIdx.x;
+    int cls = i < n ? topk_class(keys, validity, i, key_mode, thr, null_class, valid_class)
+                    : TOPK_AFTER;
+    nb += cls == TOPK_BEFORE;
+    nt += cls == TOPK_TIE;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    nb += __shfl_down(nb, off);
+    nt += __shfl_down(nt, off);
+  }
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+    if (nb) atomicAdd(&c[0], nb);
+    if (nt) atomicAdd(&c[1], nt);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    cnt[blockIdx.x] = c[0];
+    cnt[nblocks + blockIdx.x] = c[1];
+  }
+}
+
+/* emit phase 2: scan is the exclusive prefix sum of cnt, so scan[b] is the
+ * number of before rows ahead of block b and scan[nblocks + b] - n_before_rows
+ * the number of tie rows ahead of it. A before row is always written; a tie
+ * row when its ordinal within T is below tie_take (|T| with keep_ties). With
+ * bb / tt the before / tie rows ahead of a row inside its block, the row's
+ * slot is before_prefix + bb + min(tie_prefix + tt, tie_take): ascending row
+ * ids. In-block ranks: wave ballot + popcount, then an LDS scan over the
+ * waves (double-buffered by round parity: one barrier per round). */
+__global__ __launch_bounds__(TOPK_BLOCK)
+void k_topk_emit(int64_t n, const uint64_t* keys, const uint8_t* validity,
+                 int key_mode, uint64_t thr, int null_class, int valid_class,
+                 const uint32_t* scan, uint32_t nblocks, uint32_t n_before_rows,
+                 uint32_t tie_take, uint32_t* out_rids, int64_t out_capacity) {
+  __shared__ uint32_t wtot[2][TOPK_WAVES][2];
+  const int wave = threadIdx.x / WAVE;
+  const unsigned long long lt = (1ULL << (threadIdx.x & (WAVE - 1))) - 1;
+  int64_t base = (int64_t)blockIdx.x * TOPK_EMIT_TILE;
+  int cls[TOPK_EMIT_ITEMS];
+  #pragma unroll
+  for (int r = 0; r < TOPK_EMIT_ITEMS; r++) {
+    int64_t i = base + r * TOPK_BLOCK + threadIdx.x;
+    cls[r] = i < n ? topk_class(keys, validity, i, key_mode, thr, null_class, valid_class)
+                   : TOPK_AFTER;
+  }
+  uint32_t run_b = scan[blockIdx.x];
+  uint32_t run_t = scan[nblocks + blockIdx.x] - n_before_rows;
+  #pragma unroll
+  for (int r = 0; r < TOPK_EMIT_ITEMS; r++) {
+    unsigned long long mb = __ballot(cls[r] == TOPK_BEFORE);
+    unsigned long long mt = __ballot(cls[r] == TOPK_TIE);
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+      wtot[r & 1][wave][0] = (uint32_t)__popcll(mb);
+      wtot[r & 1][wave][1] = (uint32_t)__popcll(mt);
+    }
+    __syncthreads();
+    uint32_t bb = run_b + (uint32_t)__popcll(mb & lt);
+    uint32_t tt = run_t + (uint32_t)__popcll(mt & lt);
+    #pragma unroll
+    for (int w = 0; w < TOPK_WAVES; w++) {
+      uint32_t wb = wtot[r & 1][w][0], wt = wtot[r & 1][w][1];
+      if (w < wave) { bb += wb; tt += wt; }
+      run_b += wb; run_t += wt;
+    }
+    bool sel = cls[r] == TOPK_BEFORE || (cls[r] == TOPK_TIE && tt < tie_take);
+    if (sel) {
+      int64_t pos = (int64_t)bb + (tt < tie_take ? tt : tie_take);
+      if (pos < out_capacity)
+        out_rids[pos] = (uint32_t)(base + r * TOPK_BLOCK + threadIdx.x);
+    }
+  }
+}
+
+struct topk_ws {
+  uint64_t* cbuf;            /* collected encoded keys of the bucket */
+  uint32_t* hist;            /* [256] level histogram */
+  unsigned long long* stats; /* {and, or, nnull, collect cursor} */
+  uint32_t* cnt;             /* [2][emit blocks] before / tie counts */
+  uint32_t* scan;            /* exclusive prefix sums of cnt */
+  uint32_t* block_sums;
+};
+
+static void topk_ws_layout(int64_t n, topk_ws* w, char* basep, int64_t* total) {
+  int64_t nb = (n + TOPK_EMIT_TILE - 1) / TOPK_EMIT_TILE;
+  int64_t scan_blocks = (2 * nb + SCAN_TILE - 1) / SCAN_TILE + 1;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) {
+    char* p = basep ? basep + off : nullptr;
+    off += (bytes + 255) & ~255LL;
+    return p;
+  };
+  w->cbuf = (uint64_t*)take((n < TOPK_COMPACT_MAX ? n : TOPK_COMPACT_MAX) * 8);
+  w->hist = (uint32_t*)take(256 * 4);
+  w->stats = (unsigned long long*)take(4 * 8);
+  w->cnt = (uint32_t*)take(2 * nb * 4);
+  w->scan = (uint32_t*)take(2 * nb * 4);
+  w->block_sums = (uint32_t*)take(scan_blocks * 4);
+  *total = off;
+}
+
+extern "C" int64_t gpuq_topk_workspace_bytes(int64_t n) {
+  if (n < 0) n = 0;
+  topk_ws w; int64_t total;
+  topk_ws_layout(n, &w, nullptr, &total);
+  return total;
+}
+
+extern "C" int gpuq_topk_candidates(void* stream, int64_t n, gpuq_col key,
+                                    int32_t desc, int32_t nulls_first, int64_t k,
+                                    int32_t keep_ties,
+                                    uint32_t* out_rids, int64_t out_capacity,
+                                    int64_t* out_counts,
+                                    void* workspace, int64_t workspace_bytes) {
+  hipStream_t s = (hipStream_t)stream;
+  out_counts[0] = out_counts[1] = out_counts[2] = 0;
+  if (n < 0 || n > 0xFFFFFFFFLL)
+    FAIL(GPUQ_ERR_INVALID, "topk: nrows %lld out of range", (long long)n);
+  if (key.dtype != GPUQ_INT64 && key.dtype != GPUQ_FLOAT64)
+    FAIL(GPUQ_ERR_INVALID, "topk: unsupported dtype %d", key.dtype);
+  topk_ws w; int64_t need;
+  topk_ws_layout(n, &w, (char*)workspace, &need);
+  if (workspace_bytes < need)
+    FAIL(GPUQ_ERR_INVALID, "topk: workspace %lld < %lld", (long long)workspace_bytes, (long long)need);
+  if (k <= 0 || n == 0) return GPUQ_OK;
+
+  const int64_t kk = k < n ? k : n;   /* rows wanted */
+  const int64_t pos = kk - 1;         /* position in S that defines T */
+  const int key_mode = (key.dtype == GPUQ_FLOAT64 ? 2 : 1) | (desc ? 4 : 0);
+  const uint64_t* col = (const uint64_t*)key.data;
+  uint32_t hh[256];
+  unsigned long long hs[3];
+
+  /* level 0: top byte, plus the AND/OR reduction and the NULL count */
+  HIP_TRY(hipMemsetAsync(w.hist, 0, 256 * 4, s));
+  HIP_TRY(hipMemsetAsync(w.stats, 0, 32, s));
+  HIP_TRY(hipMemsetAsync(w.stats, 0xFF, 8, s));  /* bits_and = ~0 */
+  { hipEvent_t _pe = prof_begin(s);
+  k_topk_hist<<<grid1d(n, TOPK_BLOCK), TOPK_BLOCK, 0, s>>>(
+      n, col, key.validity, key_mode, 0, 0, 56, w.hist, w.stats);
+  prof_end("topk_hist", s, _pe); }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(hh, w.hist, sizeof(hh), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(hs, w.stats, sizeof(hs), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const int64_t nnull = (int64_t)hs[2], nvalid = n - nnull;
+  if (nnull < 0 || nnull > n) FAIL(GPUQ_ERR_INVALID, "topk: bad NULL count");
+
+  /* NULLs are one group at the head or the tail of S */
+  const bool t_is_null = nulls_first ? pos < nnull : pos >= nvalid;
+  int64_t n_before, n_tie;
+  uint64_t thr = 0;
+  int null_class, valid_class;
+  if (t_is_null) {
+    n_before = nulls_first ? 0 : nvalid;
+    n_tie = nnull;
+    null_class = TOPK_TIE;
+    valid_class = nulls_first ? TOPK_AFTER : TOPK_BEFORE;
+  } else {
+    const int64_t head = nulls_first ? nnull : 0;   /* NULLs ahead of the valid rows */
+    int64_t r = pos - head;       /* remaining rank inside the current bucket */
+    int64_t before = 0;           /* valid rows known to sort before the bucket */
+    int64_t bucket = nvalid;
+    const uint64_t bits_changed = hs[0] ^ hs[1];
+    uint64_t prefix = hs[0];      /* uniform bytes are right already */
+    const uint64_t* src = col;
+    const uint8_t* src_valid = key.validity;
+    int64_t n_src = n;
+    int src_mode = key_mode;
+    for (int b = 7; b >= 0; b--) {
+      if (((bits_changed >> (b * 8)) & 0xff) == 0) continue;  /* uniform byte */
+      if (b != 7) {   /* level 0 already counted byte 7 into hh */
+        const uint64_t mask = ~0ULL << ((b + 1) * 8);
+        HIP_TRY(hipMemsetAsync(w.hist, 0, 256 * 4, s));
+        if (src == col && bucket <= TOPK_COMPACT_MAX) {
+          { hipEvent_t _pe = prof_begin(s);
+          k_topk_collect<<<grid1d(n, TOPK_BLOCK), TOPK_BLOCK, 0, s>>>(
+              n, col, key.validity, key_mode, prefix, mask, b * 8, w.hist,
+              w.cbuf, (unsigned int*)&w.stats[3], (uint32_t)bucket);
+          prof_end("topk_collect", s, _pe); }
+          src = w.cbuf; src_valid = nullptr; n_src = bucket; src_mode = 0;
+        } else {
+          { hipEvent_t _pe = prof_begin(s);
+          k_topk_hist<<<grid1d(n_src, TOPK_BLOCK), TOPK_BLOCK, 0, s>>>(
+              n_src, src, src_valid, src_mode, prefix, mask, b * 8, w.hist, nullptr);
+          prof_end("topk_hist", s, _pe); }
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(hh, w.hist, sizeof(hh), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+      }
+      int64_t cum = 0;
+      int d = 0;
+      for (; d < 256; d++) {
+        if (r < cum + (int64_t)hh[d]) break;
+        cum += hh[d];
+      }
+      if (d == 256)
+        FAIL(GPUQ_ERR_INVALID, "topk: level counts do not add up (key column changed during the call?)");
+      before += cum;
+      r -= cum;
+      bucket = hh[d];
+      prefix = (prefix & ~(0xffULL << (b * 8))) | ((uint64_t)d << (b * 8));
+    }
+    thr = prefix;
+    n_before = head + before;
+    n_tie = bucket;
+    null_class = nulls_first ? TOPK_BEFORE : TOPK_AFTER;
+    valid_class = -1;
+  }
+  const int64_t tie_take = keep_ties ? n_tie : kk - n_before;
+  if (tie_take < 1 || tie_take > n_tie)
+    FAIL(GPUQ_ERR_INVALID, "topk: inconsistent counts (key column changed during the call?)");
+  const int64_t n_cand = n_before + tie_take;
+  out_counts[0] = n_cand; out_counts[1] = n_before; out_counts[2] = n_tie;
+  if (n_cand > out_capacity)
+    FAIL(GPUQ_ERR_OVERFLOW, "topk: %lld candidates > out_capacity %lld",
+         (long long)n_cand, (long long)out_capacity);
+
+  /* emit: per-block (before, tie) counts, one scan over both, ranked write */
+  const int64_t nb = (n + TOPK_EMIT_TILE - 1) / TOPK_EMIT_TILE;
+  hipEvent_t _pe = prof_begin(s);
+  k_topk_count<<<dim3((uint32_t)nb), TOPK_BLOCK, 0, s>>>(
+      n, col, key.validity, key_mode, thr, null_class, valid_class, w.cnt, (uint32_t)nb);
+  HIP_TRY(hipGetLastError());
+  int rc = exclusive_scan_u32(s, 2 * nb, w.cnt, w.scan, w.block_sums);
+  if (rc) return rc;
+  k_topk_emit<<<dim3((uint32_t)nb), TOPK_BLOCK, 0, s>>>(
+      n, col, key.validity, key_mode, thr, null_class, valid_class, w.scan,
+      (uint32_t)nb, (uint32_t)n_before, (uint32_t)tie_take, out_rids, out_capacity);
+  prof_end("topk_emit", s, _pe);
+  HIP_TRY(hipGetLastError());
+  return GPUQ_OK;
+}
+
 /* ---- partition: one ranked-scatter pass with bin = partition id ---- */
 
 /* pack (validity, key) into the u64 slot used by compute_bin<1>:

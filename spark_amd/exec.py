@@ -136,6 +136,73 @@ class SortExec(_CpuNode):
         return self.sort_orders
 
 
+class TakeOrderedAndProjectExec(_CpuNode):
+    """ORDER BY ... LIMIT k as Catalyst plans it (execution/limit.scala
+    TakeOrderedAndProjectExec), not Sort + Limit. sort_order: one SortOrder or
+    a list; project_list: None (all child columns) or a list of column
+    names."""
+
+    def __init__(self, limit: int, sort_order, project_list, child):
+        super().__init__(child)
+        assert limit >= 0
+        self.limit, self.sort_order = limit, sort_order
+        self.project_list = project_list
+
+    @property
+    def sort_orders(self):
+        return ([self.sort_order] if isinstance(self.sort_order, SortOrder)
+                else list(self.sort_order))
+
+    @property
+    def output(self):
+        if self.project_list is None:
+            return self.children[0].output
+        return list(self.project_list)
+
+    @property
+    def output_ordering(self):
+        return self.sort_orders
+
+
+class LocalLimitExec(_CpuNode):
+    """First `limit` rows of each partition (limit.scala LocalLimitExec)."""
+
+    def __init__(self, limit: int, child):
+        super().__init__(child)
+        assert limit >= 0
+        self.limit = limit
+
+    @property
+    def output(self):
+        return self.children[0].output
+
+    @property
+    def output_ordering(self):
+        return self.children[0].output_ordering
+
+
+class GlobalLimitExec(_CpuNode):
+    """First `limit` rows after `offset` of the single partition
+    (limit.scala GlobalLimitExec)."""
+
+    def __init__(self, limit: int, child, offset: int = 0):
+        super().__init__(child)
+        assert limit >= 0 and offset >= 0
+        self.limit, self.offset = limit, offset
+
+    @property
+    def output(self):
+        return self.children[0].output
+
+    @property
+    def output_ordering(self):
+        return self.children[0].output_ordering
+
+
+class CollectLimitExec(GlobalLimitExec):
+    """limit.scala CollectLimitExec: the same shape, as the plan's root."""
+
+
 class HashAggregateExec(_CpuNode):
     """group_key: one column name or a tuple of names (composite GROUP BY,
     the UnsafeRow key-tuple case)."""
@@ -504,6 +571,205 @@ class GpuSortExec(SparkPlan):
             for o in reversed(orders):
                 batch = self._sort_pass(batch, o)
             yield batch
+
+
+def _gather_batch(batch, perm):
+    """every column and bitmap of batch through one row permutation (gather
+    / gather_bits: the bitmap comes out clean, nothing is sliced)."""
+    from . import gpuq
+    cols, validity = {}, {}
+    for name, t in batch.columns().items():
+        cols[name] = gpuq.gather(t, perm)
+        v = batch.validity(name)
+        if v is not None and perm.numel():
+            validity[name] = gpuq.gather_bits(v, perm)
+    batch.close()
+    return ColumnarBatch(cols, validity=validity or None)
+
+
+def _row_range(lo: int, hi: int):
+    """identity permutation over rows [lo, hi) (int32, the gather kernels'
+    u32 row ids)."""
+    return torch.arange(lo, hi, dtype=torch.int32, device="cuda")
+
+
+# TakeOrdered runs sort + head instead of the select when
+# limit > rows * TOPK_SORT_FRACTION: the largest measured k/n at which
+# topk_perm still beats sort + head beyond the run-to-run spread, for int64
+# and float64 keys at 2^26 and 2^28 rows (DESIGN.md "Top-K (radix select)",
+# table rows "n/8"; at n/2 the sort wins).
+TOPK_SORT_FRACTION = 1.0 / 8
+
+
+class GpuTakeOrderedAndProjectExec(SparkPlan):
+    """Replaces TakeOrderedAndProjectExec (limit.scala): per child batch, a
+    radix select on the first sort key (gpuq.topk_candidates; boundary ties
+    kept whole when further keys break them) leaves at most limit rows plus
+    ties, which alone are gathered and stable-sorted from the last key to the
+    first; the heads of all batches concatenate in batch order and reduce once
+    more the same way. Every stage is stable and keeps input order, so the
+    result equals the first `limit` rows of GpuSortExec over the concatenated
+    child, boundary ties included, while memory stays bounded by batches x
+    limit rows. Above limit > rows * TOPK_SORT_FRACTION a batch is sorted
+    whole instead (identical result)."""
+
+    def __init__(self, limit: int, sort_order, project_list, child):
+        super().__init__(child)
+        assert limit >= 0
+        self.limit, self.sort_order = limit, sort_order
+        self.project_list = project_list
+
+    @property
+    def sort_orders(self):
+        return ([self.sort_order] if isinstance(self.sort_order, SortOrder)
+                else list(self.sort_order))
+
+    @property
+    def output(self):
+        if self.project_list is None:
+            return self.children[0].output
+        return list(self.project_list)
+
+    @property
+    def output_ordering(self):
+        return self.sort_orders
+
+    @property
+    def supports_columnar(self):
+        return True
+
+    def _head(self, batch):
+        """the first min(limit, rows) rows of batch in sort order."""
+        from . import gpuq
+        orders = self.sort_orders
+        rows = batch.num_rows()
+        keep = min(self.limit, rows)
+        if rows == 0:
+            return batch
+        if self.limit <= rows * TOPK_SORT_FRACTION:
+            o = orders[0]
+            rids, _, _ = gpuq.topk_candidates(
+                batch.column(o.key), self.limit, desc=o.descending,
+                nulls_first=o.nulls_first, key_validity=batch.validity(o.key),
+                keep_ties=len(orders) > 1)
+            batch = _gather_batch(batch, rids)
+        for o in reversed(orders):
+            batch = GpuSortExec._sort_pass(batch, o)
+        if batch.num_rows() > keep:
+            batch = _gather_batch(batch, _row_range(0, keep))
+        return batch
+
+    def execute_columnar(self):
+        import torch.distributed as dist
+        from . import gpuq  # noqa: F401 (engine presence check)
+        # the merge across ranks would be a broadcast_gather of the local
+        # heads plus one more reduction
+        assert not (dist.is_initialized() and dist.get_world_size() > 1), \
+            "multi-rank TakeOrdered unsupported"
+        child = self.children[0].execute_columnar()
+        if self.limit == 0:
+            first = next(child)
+            heads = [ColumnarBatch({n_: t[:0]
+                                    for n_, t in first.columns().items()})]
+            first.close()
+        else:
+            heads = [self._head(b) for b in child]
+        assert heads, "TakeOrdered over a batchless child"
+        out = heads[0] if len(heads) == 1 else self._head(concat_batches(heads))
+        if self.project_list is not None:
+            cols = {n_: out.column(n_) for n_ in self.project_list}
+            validity = {n_: out.validity(n_) for n_ in self.project_list
+                        if out.validity(n_) is not None}
+            out = ColumnarBatch(cols, validity=validity or None)
+        yield out
+
+
+class GpuLocalLimitExec(SparkPlan):
+    """Replaces LocalLimitExec (limit.scala): the first `limit` rows across
+    the child's batches in order; no batch is pulled once they are out. Data
+    columns are tensor slices; bitmaps go through gather_bits with an
+    identity row range, because the cut is not byte-aligned."""
+
+    offset = 0
+
+    def __init__(self, limit: int, child):
+        super().__init__(child)
+        assert limit >= 0
+        self.limit = limit
+
+    @property
+    def output(self):
+        return self.children[0].output
+
+    @property
+    def output_ordering(self):
+        return self.children[0].output_ordering
+
+    @property
+    def supports_columnar(self):
+        return True
+
+    @staticmethod
+    def _slice(batch, lo: int, hi: int):
+        from . import gpuq
+        cols = {n_: t[lo:hi] for n_, t in batch.columns().items()}
+        validity = {}
+        if hi > lo:
+            rows = _row_range(lo, hi)
+            for n_ in cols:
+                v = batch.validity(n_)
+                if v is not None:
+                    validity[n_] = gpuq.gather_bits(v, rows)
+        batch.close()
+        return ColumnarBatch(cols, validity=validity or None)
+
+    def execute_columnar(self):
+        from . import gpuq  # noqa: F401 (engine presence check)
+        skip, remaining = self.offset, self.limit
+        empty = None            # schema carrier if no row comes out
+        emitted = False
+        for batch in self.children[0].execute_columnar():
+            rows = batch.num_rows()
+            lo = min(skip, rows)
+            skip -= lo
+            take = min(rows - lo, remaining)
+            remaining -= take
+            if take == rows:
+                emitted = True
+                yield batch
+            elif take > 0:
+                emitted = True
+                yield self._slice(batch, lo, lo + take)
+            elif empty is None:
+                empty = self._slice(batch, 0, 0)
+            if remaining == 0:
+                break
+        if not emitted:
+            assert empty is not None, "limit over a batchless child"
+            yield empty
+
+
+class GpuGlobalLimitExec(GpuLocalLimitExec):
+    """Replaces GlobalLimitExec (limit.scala): the first `limit` rows after
+    `offset` of the single partition (AllTuples)."""
+
+    def __init__(self, limit: int, child, offset: int = 0):
+        super().__init__(limit, child)
+        assert offset >= 0
+        self.offset = offset
+
+    def required_child_distribution(self):
+        return [Distribution("all_tuples")]
+
+    def execute_columnar(self):
+        import torch.distributed as dist
+        assert not (dist.is_initialized() and dist.get_world_size() > 1), \
+            "multi-rank GlobalLimit unsupported"
+        yield from super().execute_columnar()
+
+
+class GpuCollectLimitExec(GpuGlobalLimitExec):
+    """Replaces CollectLimitExec: GlobalLimit as the plan's root."""
 
 
 class GpuHashAggregateExec(SparkPlan):
@@ -1343,6 +1609,17 @@ class GpuColumnarRule:
         children = [self.pre_columnar_transitions(c) for c in plan.children]
         if isinstance(plan, SortExec):
             return GpuSortExec(plan.sort_order, plan.global_sort, *children)
+        if isinstance(plan, TakeOrderedAndProjectExec):
+            return GpuTakeOrderedAndProjectExec(
+                plan.limit, plan.sort_order, plan.project_list, *children)
+        if isinstance(plan, LocalLimitExec):
+            return GpuLocalLimitExec(plan.limit, *children)
+        if isinstance(plan, CollectLimitExec):   # before its base class
+            return GpuCollectLimitExec(plan.limit, *children,
+                                       offset=plan.offset)
+        if isinstance(plan, GlobalLimitExec):
+            return GpuGlobalLimitExec(plan.limit, *children,
+                                      offset=plan.offset)
         if isinstance(plan, HashAggregateExec):
             return GpuHashAggregateExec(
                 plan.group_key, plan.aggs, plan.mode, *children,

@@ -59,6 +59,12 @@ def lib() -> ctypes.CDLL:
         L.gpuq_sort_workspace_bytes.argtypes = [i64]
         L.gpuq_sort_perm.restype = i32
         L.gpuq_sort_perm.argtypes = [vp, i64, _Col, i32, i32, vp, vp, vp, i64]
+        L.gpuq_topk_workspace_bytes.restype = i64
+        L.gpuq_topk_workspace_bytes.argtypes = [i64]
+        L.gpuq_topk_candidates.restype = i32
+        L.gpuq_topk_candidates.argtypes = [vp, i64, _Col, i32, i32, i64, i32,
+                                           vp, i64, ctypes.POINTER(i64),
+                                           vp, i64]
         L.gpuq_gather.restype = i32
         L.gpuq_gather.argtypes = [vp, i64, _Col, vp, vp]
         L.gpuq_gather2_i64.restype = i32
@@ -259,6 +265,68 @@ def sort_last_plan():
     wp, db, fb = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     lib().gpuq_sort_last_plan(ctypes.byref(wp), ctypes.byref(db), ctypes.byref(fb))
     return wp.value, db.value, fb.value
+
+
+# mirrors of the #defines in csrc/gpuq.hip: the bucket size below which the
+# select copies the surviving keys to its workspace, and the emit kernels'
+# rows per block
+TOPK_COMPACT_MAX = 1 << 20
+TOPK_EMIT_TILE = 2048
+
+
+def topk_workspace(n: int, device="cuda") -> torch.Tensor:
+    return torch.empty(lib().gpuq_topk_workspace_bytes(n), dtype=torch.uint8,
+                       device=device)
+
+
+def topk_candidates(keys: torch.Tensor, k: int, desc=False, nulls_first=None,
+                    key_validity=None, keep_ties=False, workspace=None):
+    """Rows of the first k positions of sort_perm(keys, desc, nulls_first)'s
+    order, by radix select. Returns (rids, n_before, n_tie): rids (int32, u32
+    bits) ascending, n_before rows sorting strictly before the tie group T
+    that holds position min(k, n) - 1, n_tie = |T|. keep_ties=False takes the
+    first min(k, n) - n_before rows of T in input order (len(rids) ==
+    min(k, n)); keep_ties=True takes all of T."""
+    n = keys.numel()
+    dev = keys.device
+    if nulls_first is None:
+        nulls_first = not desc
+    if workspace is None:
+        workspace = topk_workspace(n, dev)
+    kk = max(min(n, k), 0)
+    cap = kk if not keep_ties else min(n, max(2 * kk, 1024))
+    counts = (ctypes.c_int64 * 3)()
+    for _ in range(2):
+        rids = torch.empty(cap, dtype=torch.int32, device=dev)
+        rc = lib().gpuq_topk_candidates(
+            _stream(), n, _col(keys, key_validity), int(desc), int(nulls_first),
+            k, int(keep_ties), rids.data_ptr(), cap, counts,
+            workspace.data_ptr(), workspace.numel())
+        if rc != 3:  # GPUQ_ERR_OVERFLOW: retry once at the reported n_cand
+            break
+        cap = counts[0]
+    _check(rc)
+    return rids[:counts[0]], counts[1], counts[2]
+
+
+def topk_perm(keys: torch.Tensor, k: int, desc=False, nulls_first=None,
+              key_validity=None):
+    """(perm, sorted_keys), each of length min(k, n): bit-identical to the
+    first k entries of sort_perm(keys, desc, nulls_first, key_validity).
+    Select the candidate rows, then stable-sort only those: they come in
+    input order, so ties resolve as in the full sort."""
+    if nulls_first is None:
+        nulls_first = not desc
+    rids, _, _ = topk_candidates(keys, k, desc=desc, nulls_first=nulls_first,
+                                 key_validity=key_validity, keep_ties=False)
+    if rids.numel() == 0:
+        return rids, torch.empty(0, dtype=keys.dtype, device=keys.device)
+    small = gather(keys, rids)
+    small_valid = gather_bits(key_validity, rids) \
+        if key_validity is not None else None
+    small_perm, skeys = sort_perm(small, desc=desc, nulls_first=nulls_first,
+                                  key_validity=small_valid)
+    return gather(rids, small_perm), skeys
 
 
 def gather(col: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
