@@ -448,8 +448,9 @@ int gpuq_join_keys_unmatched_build(void* stream, void* workspace, int64_t capaci
 /* ---------------------------------------------------------------- */
 /* FILTER / PROJECT — SURVEY §8(f).2: FilterExec / ProjectExec on    */
 /* columnar batches, so multi-operator plans stay on-device.         */
-/* Filter: single comparison col OP literal; WHERE keeps only TRUE   */
-/* (NULL comparison result drops the row). Stable compaction: the    */
+/* Filter: single comparison col OP literal (gpuq_filter_cmp) or a   */
+/* compound predicate (gpuq_filter_expr); WHERE keeps only TRUE      */
+/* (a NULL result drops the row). Stable compaction: the             */
 /* first *out_count entries of out_perm are the passing rows in      */
 /* input order. Project: elementwise a OP b (column or literal).     */
 /* ---------------------------------------------------------------- */
@@ -474,6 +475,72 @@ int gpuq_filter_cmp(void* stream, int64_t nrows, gpuq_col col, int32_t op,
                     double lit_f64, int64_t lit_i64,
                     uint32_t* out_perm, int64_t* out_count /* device, u64 */,
                     void* workspace, int64_t workspace_bytes);
+
+/* Compound WHERE predicate in one fused pass: a postfix program over up to
+ * GPUQ_PRED_MAX_COLS columns, evaluated per row on a stack of three-valued
+ * (TRUE / FALSE / NULL) slots. The host layer lowers And / Or / Not / In /
+ * Between / IsNull / IsNotNull and the binary comparisons to it; the kernel
+ * knows only the eight opcodes below.
+ *
+ * Semantics (Spark, non-ANSI):
+ *  - CMP_LIT (cols[col_a] OP literal; lit_f64 for a float64 column, lit_i64
+ *    for an int64 one) and CMP_COL (cols[col_a] OP cols[col_b], equal
+ *    dtypes): NULL if an operand row is NULL, else exactly the comparison
+ *    rules above — total order on float64, -0.0 == 0.0, NaN == NaN and
+ *    greatest;
+ *  - IS_NULL / IS_NOT_NULL push TRUE or FALSE, never NULL;
+ *  - CONST pushes cmp: 0 = FALSE, 1 = TRUE, 2 = NULL;
+ *  - AND pops two: FALSE if either is FALSE, else NULL if either is NULL,
+ *    else TRUE. OR is its dual: TRUE if either is TRUE, else NULL if either
+ *    is NULL, else FALSE. NOT pops one: NOT NULL is NULL;
+ *  - a row passes iff the value left on the stack is TRUE. */
+#define GPUQ_PRED_CMP_LIT 0
+#define GPUQ_PRED_CMP_COL 1
+#define GPUQ_PRED_IS_NULL 2
+#define GPUQ_PRED_IS_NOT_NULL 3
+#define GPUQ_PRED_CONST 4
+#define GPUQ_PRED_AND 5
+#define GPUQ_PRED_OR 6
+#define GPUQ_PRED_NOT 7
+
+#define GPUQ_PRED_FALSE 0
+#define GPUQ_PRED_TRUE 1
+#define GPUQ_PRED_NULL 2
+
+#define GPUQ_PRED_MAX_INSNS 32
+#define GPUQ_PRED_MAX_COLS 8
+#define GPUQ_PRED_MAX_DEPTH 16
+
+typedef struct gpuq_pred_insn {
+  int32_t opcode;   /* GPUQ_PRED_* */
+  int32_t cmp;      /* GPUQ_CMP_* for CMP_LIT / CMP_COL; 0/1/2 = FALSE/TRUE/NULL for CONST */
+  int32_t col_a;    /* index into cols[] */
+  int32_t col_b;    /* CMP_COL only */
+  int64_t lit_i64;
+  double lit_f64;
+} gpuq_pred_insn;
+
+/* workspace bytes for gpuq_filter_expr at nrows; pure arithmetic */
+int64_t gpuq_filter_expr_workspace_bytes(int64_t nrows);
+
+/* The first *out_count entries of out_perm[nrows] are the row ids for which
+ * the program evaluates to TRUE, in ascending (input) order; entries past
+ * *out_count are unspecified (gpuq_filter_cmp writes all nrows, this does
+ * not). prog is a HOST array, copied into the kernel arguments. Each
+ * referenced column (and bitmap) is read once and never written. nrows == 0
+ * sets *out_count to 0 and launches nothing. Returned as GPUQ_ERR_INVALID
+ * before anything is launched: nrows > 0xFFFFFFFF; ncols outside
+ * 0..GPUQ_PRED_MAX_COLS (a CONST-only program reads no column; cols may be
+ * NULL then) or ninsns outside 1..GPUQ_PRED_MAX_INSNS; a bad
+ * opcode, comparison code or CONST value; a column index out of range; a
+ * column whose dtype is not int64 / float64; CMP_COL over two dtypes; a
+ * short workspace; a program whose stack underflows, grows past
+ * GPUQ_PRED_MAX_DEPTH or does not end at depth exactly 1. */
+int gpuq_filter_expr(void* stream, int64_t nrows,
+                     const gpuq_col* cols, int32_t ncols,
+                     const gpuq_pred_insn* prog /* HOST */, int32_t ninsns,
+                     uint32_t* out_perm, int64_t* out_count /* device, u64 */,
+                     void* workspace, int64_t workspace_bytes);
 
 #define GPUQ_BINOP_ADD 0
 #define GPUQ_BINOP_SUB 1

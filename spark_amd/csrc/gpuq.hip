@@ -5188,6 +5188,335 @@ extern "C" int gpuq_filter_cmp(void* stream, int64_t n, gpuq_col col, int32_t op
   return GPUQ_OK;
 }
 
+/* ---- compound predicates: one fused pass (gpuq_filter_expr) ----
+ *
+ *  mask  k_pred_mask: one block per PRED_TILE rows interprets the postfix
+ *        program over its rows and writes one pass bit per row (a 64-bit
+ *        ballot word per wave and round) plus the block's pass count.
+ *  scan  exclusive_scan_u32 over the block counts.
+ *  emit  k_pred_emit: reads only its tile's mask words and writes the row id
+ *        of every set bit at scan[block] + rank inside the tile.
+ * Two bounded phases, no lookback and no spin (the top-k emit's shape). The
+ * columns are read once, by the mask kernel.
+ */
+#define PRED_BLOCK 256
+#define PRED_WAVES (PRED_BLOCK / WAVE)
+#define PRED_ITEMS 8
+#define PRED_TILE (PRED_BLOCK * PRED_ITEMS)   /* 2048 rows per block */
+#define PRED_WORDS (PRED_TILE / WAVE)         /* 32 mask words per block */
+
+/* column table and program, passed by value in the kernel arguments */
+struct pred_args {
+  const void* data[GPUQ_PRED_MAX_COLS];
+  const uint8_t* validity[GPUQ_PRED_MAX_COLS];
+  int32_t dtype[GPUQ_PRED_MAX_COLS];
+  int32_t ninsns;
+  gpuq_pred_insn insn[GPUQ_PRED_MAX_INSNS];
+};
+
+/* Row r of thread t is base + r * PRED_BLOCK + t: for each r a wave covers 64
+ * consecutive rows, so its ballot is mask word r * PRED_WAVES + wave of the
+ * tile and the words ascend in row order. The program counter is the same in
+ * every lane (the program comes from the kernel arguments), so the
+ * interpreter's branches are wave-uniform. Instructions outer, the 8 rows
+ * inner and unrolled: a leaf issues its 8 loads back to back.
+ *
+ * The per-row evaluation stack is two 32-bit words: bit d of tb[r] / nb[r] is
+ * the TRUE / NULL flag of stack slot d (slot 0 = top; never both set; both
+ * clear = FALSE). A push shifts left and ors the new flag in; AND / OR / NOT
+ * rewrite the low bits. Nothing is indexed by a runtime value.
+ *
+ * cv / cvalid cache the most recently loaded col_a (8 values and validity
+ * bits per thread): consecutive leaves on one column — BETWEEN, IN — load it
+ * once. */
+__global__ __launch_bounds__(PRED_BLOCK)
+void k_pred_mask(int64_t n, pred_args a, unsigned long long* mask, uint32_t* cnt) {
+  __shared__ uint32_t wcnt[PRED_WAVES];
+  const int64_t base = (int64_t)blockIdx.x * PRED_TILE + threadIdx.x;
+  uint32_t tb[PRED_ITEMS], nb[PRED_ITEMS];
+  uint64_t cv[PRED_ITEMS];
+  uint32_t cvalid = 0;
+  int cached = -1;
+  #pragma unroll
+  for (int r = 0; r < PRED_ITEMS; r++) { tb[r] = 0; nb[r] = 0; cv[r] = 0; }
+
+  for (int pc = 0; pc < a.ninsns; pc++) {
+    const int opcode = a.insn[pc].opcode;
+    if (opcode <= GPUQ_PRED_IS_NOT_NULL) {
+      const int ca = a.insn[pc].col_a;
+      if (ca != cached) {
+        const uint64_t* d = (const uint64_t*)a.data[ca];
+        const uint8_t* v = a.validity[ca];
+        cvalid = 0;
+        #pragma unroll
+        for (int r = 0; r < PRED_ITEMS; r++) {
+          int64_t i = base + r * PRED_BLOCK;
+          bool in = i < n;
+          cv[r] = in ? d[i] : 0;
+          cvalid |= (uint32_t)(in && bit_valid(v, i)) << r;
+        }
+        cached = ca;
+      }
+      if (opcode == GPUQ_PRED_CMP_LIT) {
+        const int op = a.insn[pc].cmp;
+        if (a.dtype[ca] == GPUQ_FLOAT64) {
+          const double lit = a.insn[pc].lit_f64;
+          #pragma unroll
+          for (int r = 0; r < PRED_ITEMS; r++) {
+            uint32_t ok = (cvalid >> r) & 1;
+            uint32_t t = filter_cmp_f64(__longlong_as_double((long long)cv[r]), op, lit);
+            tb[r] = (tb[r] << 1) | (t & ok);
+            nb[r] = (nb[r] << 1) | (ok ^ 1);
+          }
+        } else {
+          const int64_t lit = a.insn[pc].lit_i64;
+          #pragma unroll
+          for (int r = 0; r < PRED_ITEMS; r++) {
+            uint32_t ok = (cvalid >> r) & 1;
+            uint32_t t = filter_cmp_i64((int64_t)cv[r], op, lit);
+            tb[r] = (tb[r] << 1) | (t & ok);
+            nb[r] = (nb[r] << 1) | (ok ^ 1);
+          }
+        }
+      } else if (opcode == GPUQ_PRED_CMP_COL) {
+        const int op = a.insn[pc].cmp;
+        const int cb = a.insn[pc].col_b;
+        const uint64_t* d = (const uint64_t*)a.data[cb];
+        const uint8_t* v = a.validity[cb];
+        const bool f64 = a.dtype[ca] == GPUQ_FLOAT64;
+        uint64_t bv[PRED_ITEMS];
+        uint32_t bvalid = 0;
+        #pragma unroll
+        for (int r = 0; r < PRED_ITEMS; r++) {
+          int64_t i = base + r * PRED_BLOCK;
+          bool in = i < n;
+          bv[r] = in ? d[i] : 0;
+          bvalid |= (uint32_t)(in && bit_valid(v, i)) << r;
+        }
+        bvalid &= cvalid;
+        #pragma unroll
+        for (int r = 0; r < PRED_ITEMS; r++) {
+          uint32_t ok = (bvalid >> r) & 1;
+          uint32_t t = f64
+              ? filter_cmp_f64(__longlong_as_double((long long)cv[r]), op,
+                               __longlong_as_double((long long)bv[r]))
+              : filter_cmp_i64((int64_t)cv[r], op, (int64_t)bv[r]);
+          tb[r] = (tb[r] << 1) | (t & ok);
+          nb[r] = (nb[r] << 1) | (ok ^ 1);
+        }
+      } else {   /* IS_NULL / IS_NOT_NULL */
+        const uint32_t flip = opcode == GPUQ_PRED_IS_NULL ? 1u : 0u;
+        #pragma unroll
+        for (int r = 0; r < PRED_ITEMS; r++) {
+          tb[r] = (tb[r] << 1) | (((cvalid >> r) & 1) ^ flip);
+          nb[r] = nb[r] << 1;
+        }
+      }
+    } else if (opcode == GPUQ_PRED_CONST) {
+      const uint32_t t = a.insn[pc].cmp == GPUQ_PRED_TRUE;
+      const uint32_t nl = a.insn[pc].cmp == GPUQ_PRED_NULL;
+      #pragma unroll
+      for (int r = 0; r < PRED_ITEMS; r++) {
+        tb[r] = (tb[r] << 1) | t;
+        nb[r] = (nb[r] << 1) | nl;
+      }
+    } else if (opcode == GPUQ_PRED_AND) {
+      #pragma unroll
+      for (int r = 0; r < PRED_ITEMS; r++) {
+        uint32_t T = tb[r], N = nb[r];
+        uint32_t rt = (T >> 1) & T & 1;
+        /* NULL unless a side is FALSE: both sides TRUE-or-NULL, one NULL */
+        uint32_t rn = ((N >> 1) | N) & ((T >> 1) | (N >> 1)) & (T | N) & 1;
+        tb[r] = ((T >> 1) & ~1u) | rt;
+        nb[r] = ((N >> 1) & ~1u) | rn;
+      }
+    } else if (opcode == GPUQ_PRED_OR) {
+      #pragma unroll
+      for (int r = 0; r < PRED_ITEMS; r++) {
+        uint32_t T = tb[r], N = nb[r];
+        uint32_t rt = ((T >> 1) | T) & 1;
+        uint32_t rn = ((N >> 1) | N) & ~rt & 1;
+        tb[r] = ((T >> 1) & ~1u) | rt;
+        nb[r] = ((N >> 1) & ~1u) | rn;
+      }
+    } else {   /* NOT: FALSE <-> TRUE, NULL stays */
+      #pragma unroll
+      for (int r = 0; r < PRED_ITEMS; r++)
+        tb[r] = (tb[r] & ~1u) | (~(tb[r] | nb[r]) & 1);
+    }
+  }
+
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  uint32_t total = 0;
+  #pragma unroll
+  for (int r = 0; r < PRED_ITEMS; r++) {
+    bool pass = (tb[r] & 1) && base + r * PRED_BLOCK < n;
+    unsigned long long m = __ballot(pass);
+    total += (uint32_t)__popcll(m);
+    if (lane == 0)
+      mask[(int64_t)blockIdx.x * PRED_WORDS + r * PRED_WAVES + wave] = m;
+  }
+  if (lane == 0) wcnt[wave] = total;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t c = 0;
+    #pragma unroll
+    for (int w = 0; w < PRED_WAVES; w++) c += wcnt[w];
+    cnt[blockIdx.x] = c;
+  }
+}
+
+/* scan[b] passing rows precede block b's tile. The block loads its 32 mask
+ * words, prefixes their popcounts in LDS (one wave scan), and the lane of
+ * each set bit writes its row id at scan[b] + word prefix + rank in the word.
+ * At most n bits are set in all (rows >= n contribute 0), so every slot is
+ * below n. The last block also writes the total. */
+__global__ __launch_bounds__(PRED_BLOCK)
+void k_pred_emit(const unsigned long long* mask, const uint32_t* scan,
+                 uint32_t nblocks, uint32_t* out_perm,
+                 unsigned long long* out_count) {
+  __shared__ unsigned long long words[PRED_WORDS];
+  __shared__ uint32_t wpre[PRED_WORDS + 1];
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  if (wave == 0) {
+    unsigned long long m = lane < PRED_WORDS
+        ? mask[(int64_t)blockIdx.x * PRED_WORDS + lane] : 0ull;
+    uint32_t c = (uint32_t)__popcll(m);
+    uint32_t inc = wave_inclusive_scan(c);
+    if (lane < PRED_WORDS) { words[lane] = m; wpre[lane] = inc - c; }
+    if (lane == PRED_WORDS - 1) wpre[PRED_WORDS] = inc;
+  }
+  __syncthreads();
+  const uint32_t start = scan[blockIdx.x];
+  const unsigned long long lt = (1ULL << lane) - 1;
+  const int64_t base = (int64_t)blockIdx.x * PRED_TILE + threadIdx.x;
+  #pragma unroll
+  for (int r = 0; r < PRED_ITEMS; r++) {
+    const int w = r * PRED_WAVES + wave;
+    unsigned long long m = words[w];
+    if ((m >> lane) & 1)
+      out_perm[start + wpre[w] + (uint32_t)__popcll(m & lt)] =
+          (uint32_t)(base + r * PRED_BLOCK);
+  }
+  if (blockIdx.x == nblocks - 1 && threadIdx.x == 0)
+    *out_count = (unsigned long long)start + wpre[PRED_WORDS];
+}
+
+struct pred_ws {
+  unsigned long long* mask;  /* [blocks][PRED_WORDS] pass bits */
+  uint32_t* cnt;             /* [blocks] pass counts */
+  uint32_t* scan;            /* exclusive prefix sums of cnt */
+  uint32_t* block_sums;
+};
+
+static void pred_ws_layout(int64_t n, pred_ws* w, char* basep, int64_t* total) {
+  int64_t nb = (n + PRED_TILE - 1) / PRED_TILE;
+  int64_t scan_blocks = (nb + SCAN_TILE - 1) / SCAN_TILE + 1;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) {
+    char* p = basep ? basep + off : nullptr;
+    off += (bytes + 255) & ~255LL;
+    return p;
+  };
+  w->mask = (unsigned long long*)take(nb * PRED_WORDS * 8);
+  w->cnt = (uint32_t*)take(nb * 4);
+  w->scan = (uint32_t*)take(nb * 4);
+  w->block_sums = (uint32_t*)take(scan_blocks * 4);
+  *total = off;
+}
+
+extern "C" int64_t gpuq_filter_expr_workspace_bytes(int64_t n) {
+  if (n < 0) n = 0;
+  pred_ws w; int64_t total;
+  pred_ws_layout(n, &w, nullptr, &total);
+  return total;
+}
+
+extern "C" int gpuq_filter_expr(void* stream, int64_t n,
+                                const gpuq_col* cols, int32_t ncols,
+                                const gpuq_pred_insn* prog, int32_t ninsns,
+                                uint32_t* out_perm, int64_t* out_count,
+                                void* workspace, int64_t workspace_bytes) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 0 || n > 0xFFFFFFFFLL)
+    FAIL(GPUQ_ERR_INVALID, "filter_expr: nrows %lld out of range", (long long)n);
+  if (ncols < 0 || ncols > GPUQ_PRED_MAX_COLS)
+    FAIL(GPUQ_ERR_INVALID, "filter_expr: %d columns, need 0..%d", ncols, GPUQ_PRED_MAX_COLS);
+  if (ninsns < 1 || ninsns > GPUQ_PRED_MAX_INSNS)
+    FAIL(GPUQ_ERR_INVALID, "filter_expr: %d instructions, need 1..%d", ninsns, GPUQ_PRED_MAX_INSNS);
+  pred_args a;
+  memset(&a, 0, sizeof(a));
+  for (int c = 0; c < ncols; c++) {
+    if (cols[c].dtype != GPUQ_INT64 && cols[c].dtype != GPUQ_FLOAT64)
+      FAIL(GPUQ_ERR_INVALID, "filter_expr: column %d has unsupported dtype %d", c, cols[c].dtype);
+    a.data[c] = cols[c].data;
+    a.validity[c] = cols[c].validity;
+    a.dtype[c] = cols[c].dtype;
+  }
+  int depth = 0;
+  for (int pc = 0; pc < ninsns; pc++) {
+    const gpuq_pred_insn& in = prog[pc];
+    int pops = 0;
+    switch (in.opcode) {
+      case GPUQ_PRED_CMP_COL:
+        if (in.col_b < 0 || in.col_b >= ncols)
+          FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: column index %d out of range", pc, in.col_b);
+        /* fallthrough */
+      case GPUQ_PRED_CMP_LIT:
+        if (in.cmp < GPUQ_CMP_EQ || in.cmp > GPUQ_CMP_NE)
+          FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: bad comparison %d", pc, in.cmp);
+        /* fallthrough */
+      case GPUQ_PRED_IS_NULL:
+      case GPUQ_PRED_IS_NOT_NULL:
+        if (in.col_a < 0 || in.col_a >= ncols)
+          FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: column index %d out of range", pc, in.col_a);
+        if (in.opcode == GPUQ_PRED_CMP_COL && cols[in.col_a].dtype != cols[in.col_b].dtype)
+          FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: column dtypes differ (%d vs %d)", pc,
+               cols[in.col_a].dtype, cols[in.col_b].dtype);
+        break;
+      case GPUQ_PRED_CONST:
+        if (in.cmp < GPUQ_PRED_FALSE || in.cmp > GPUQ_PRED_NULL)
+          FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: bad constant %d", pc, in.cmp);
+        break;
+      case GPUQ_PRED_AND:
+      case GPUQ_PRED_OR: pops = 2; break;
+      case GPUQ_PRED_NOT: pops = 1; break;
+      default:
+        FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: bad opcode %d", pc, in.opcode);
+    }
+    if (depth < pops)
+      FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: stack underflow", pc);
+    depth += 1 - pops;
+    if (depth > GPUQ_PRED_MAX_DEPTH)
+      FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: stack depth exceeds %d", pc, GPUQ_PRED_MAX_DEPTH);
+    a.insn[pc] = in;
+  }
+  if (depth != 1)
+    FAIL(GPUQ_ERR_INVALID, "filter_expr: program leaves %d values on the stack, need 1", depth);
+  a.ninsns = ninsns;
+  pred_ws w; int64_t need;
+  pred_ws_layout(n, &w, (char*)workspace, &need);
+  if (workspace_bytes < need)
+    FAIL(GPUQ_ERR_INVALID, "filter_expr: workspace %lld < %lld", (long long)workspace_bytes, (long long)need);
+  if (n == 0) {
+    HIP_TRY(hipMemsetAsync(out_count, 0, 8, s));
+    return GPUQ_OK;
+  }
+  const int64_t nb = (n + PRED_TILE - 1) / PRED_TILE;
+  { hipEvent_t _pe = prof_begin(s);
+  k_pred_mask<<<dim3((uint32_t)nb), PRED_BLOCK, 0, s>>>(n, a, w.mask, w.cnt);
+  prof_end("filter_expr_mask", s, _pe); }
+  HIP_TRY(hipGetLastError());
+  { hipEvent_t _pe = prof_begin(s);
+  int rc = exclusive_scan_u32(s, nb, w.cnt, w.scan, w.block_sums);
+  if (rc) return rc;
+  k_pred_emit<<<dim3((uint32_t)nb), PRED_BLOCK, 0, s>>>(
+      w.mask, w.scan, (uint32_t)nb, out_perm, (unsigned long long*)out_count);
+  prof_end("filter_expr_emit", s, _pe); }
+  HIP_TRY(hipGetLastError());
+  return GPUQ_OK;
+}
+
 /* One int64 operation with Java long semantics (Spark non-ANSI): + - * wrap
  * modulo 2^64, done in uint64_t because signed overflow is undefined in C++;
  * / truncates toward zero and INT64_MIN / -1 == INT64_MIN (divisor -1 is an

@@ -18,6 +18,9 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from .predicate import (And, Between, Cmp, Col, In, IsNotNull,  # noqa: F401
+                        IsNull, Not, Or, Pred)
+
 
 class ColumnarBatch:
     """Device-resident batch (ColumnarBatch.java:61-123 access contract;
@@ -316,10 +319,28 @@ class ShuffleExchangeExec(_CpuNode):
         return self.children[0].output
 
 
+def _filter_args(args):
+    """FilterExec(col, op, literal, child) or FilterExec(condition, child)
+    -> (col, op, literal, condition, child); the form not used is None."""
+    if len(args) == 4:
+        return args[0], args[1], args[2], None, args[3]
+    if len(args) == 2:
+        if not isinstance(args[0], Pred):
+            raise TypeError(f"filter condition {args[0]!r} is not a predicate")
+        return None, None, None, args[0], args[1]
+    raise TypeError("expected (col, op, literal, child) or (condition, child)")
+
+
 class FilterExec(_CpuNode):
-    def __init__(self, col: str, op: str, literal, child):
+    """FilterExec(col, op, literal, child): one col OP literal comparison.
+    FilterExec(condition, child): a predicate tree (spark_amd.predicate), the
+    shape of basicPhysicalOperators.scala FilterExec(condition, child)."""
+
+    def __init__(self, *args):
+        col, op, literal, condition, child = _filter_args(args)
         super().__init__(child)
         self.col, self.op, self.literal = col, op, literal
+        self.condition = condition
 
     @property
     def output(self):
@@ -1468,13 +1489,17 @@ class GpuRangeExec(SparkPlan):
 
 
 class GpuFilterExec(SparkPlan):
-    """Replaces FilterExec for col OP literal predicates:
-    stable compaction on device, then payload gather by the passing-row
-    permutation."""
+    """Replaces FilterExec: stable compaction on device,
+    then payload gather by the passing-row permutation. The four-argument
+    form (col, op, literal, child) runs one comparison through
+    gpuq_filter_cmp; the two-argument form (condition, child) evaluates a
+    predicate tree in one fused pass through gpuq_filter_expr."""
 
-    def __init__(self, col: str, op: str, literal, child):
+    def __init__(self, *args):
+        col, op, literal, condition, child = _filter_args(args)
         super().__init__(child)
         self.col, self.op, self.literal = col, op, literal
+        self.condition = condition
 
     @property
     def output(self):
@@ -1492,9 +1517,16 @@ class GpuFilterExec(SparkPlan):
     def execute_columnar(self):
         from . import gpuq
         for batch in self.children[0].execute_columnar():
-            perm, cnt = gpuq.filter_cmp(batch.column(self.col), self.op,
-                                        self.literal,
-                                        validity=batch.validity(self.col))
+            if self.condition is not None:
+                names = batch.columns()
+                perm, cnt = gpuq.filter_expr(
+                    names, self.condition,
+                    validities={k: batch.validity(k) for k in names
+                                if batch.validity(k) is not None})
+            else:
+                perm, cnt = gpuq.filter_cmp(batch.column(self.col), self.op,
+                                            self.literal,
+                                            validity=batch.validity(self.col))
             cols, validity = {}, {}
             for name, t in batch.columns().items():
                 cols[name] = gpuq.gather(t, perm)
@@ -1647,6 +1679,8 @@ class GpuColumnarRule:
         if isinstance(plan, ShuffleExchangeExec):
             return GpuShuffleExchangeExec(plan.keys, *children)
         if isinstance(plan, FilterExec):
+            if plan.condition is not None:
+                return GpuFilterExec(plan.condition, *children)
             return GpuFilterExec(plan.col, plan.op, plan.literal, *children)
         if isinstance(plan, ProjectExec):
             return GpuProjectExec(plan.projections, *children)

@@ -11,6 +11,9 @@ import os
 
 import torch
 
+from . import predicate
+from .predicate import rewrite_i64_float_cmp
+
 _DIR = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_DIR, "libgpuq.so")
 
@@ -33,6 +36,15 @@ class _Col(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p),
                 ("validity", ctypes.c_void_p),
                 ("dtype", ctypes.c_int32)]
+
+
+class _PredInsn(ctypes.Structure):
+    _fields_ = [("opcode", ctypes.c_int32),
+                ("cmp", ctypes.c_int32),
+                ("col_a", ctypes.c_int32),
+                ("col_b", ctypes.c_int32),
+                ("lit_i64", ctypes.c_int64),
+                ("lit_f64", ctypes.c_double)]
 
 
 _lib = None
@@ -160,6 +172,12 @@ def lib() -> ctypes.CDLL:
         L.gpuq_filter_cmp.restype = i32
         L.gpuq_filter_cmp.argtypes = [vp, i64, _Col, i32, ctypes.c_double, i64,
                                       vp, vp, vp, i64]
+        L.gpuq_filter_expr_workspace_bytes.restype = i64
+        L.gpuq_filter_expr_workspace_bytes.argtypes = [i64]
+        L.gpuq_filter_expr.restype = i32
+        L.gpuq_filter_expr.argtypes = [vp, i64, ctypes.POINTER(_Col), i32,
+                                       ctypes.POINTER(_PredInsn), i32,
+                                       vp, vp, vp, i64]
         L.gpuq_project_binop.restype = i32
         L.gpuq_project_binop.argtypes = [vp, i64, _Col, vp, ctypes.c_double, i64,
                                          i32, vp]
@@ -506,7 +524,7 @@ def join_keys_unmatched_build(workspace: torch.Tensor, capacity: int,
     return op[:nr.value], ob[:nr.value], nr.value
 
 
-CMP ={"==": 0, "<": 1, "<=": 2, ">": 3, ">=": 4, "!=": 5}
+CMP = predicate.CMP
 BINOP = {"+": 0, "-": 1, "*": 2, "/": 3, "rsub": 4}
 
 
@@ -537,32 +555,8 @@ def filter_cmp(col: torch.Tensor, op: str, literal, workspace=None, validity=Non
     predicates (NaN is greater than every double a bigint casts to)."""
     n = col.numel()
     dev = col.device
-    import math
-    I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
-    ALL, NONE = (">=", I64_MIN), ("<", I64_MIN)   # every valid row / no row
     if col.dtype == torch.int64 and isinstance(literal, float):
-        if math.isnan(literal):
-            op, literal = ALL if op in ("<", "<=", "!=") else NONE
-        elif math.isinf(literal):
-            all_ops = ("<", "<=") if literal > 0 else (">", ">=")
-            op, literal = ALL if op in all_ops or op == "!=" else NONE
-        elif literal != int(literal) \
-                or not (I64_MIN <= int(literal) <= I64_MAX):
-            f = math.floor(literal)
-            if op in ("==",):
-                op, literal = NONE
-            elif op in ("!=",):
-                op, literal = ALL
-            elif op in ("<", "<="):
-                # col < L  <=>  col <= floor(L)
-                op, literal = ("<=", f) if f >= I64_MIN else NONE
-                if f > I64_MAX:
-                    op, literal = ALL
-            else:  # > / >=  : col > L <=> col >= floor(L)+1
-                g = f + 1
-                op, literal = (">=", g) if g <= I64_MAX else NONE
-                if g < I64_MIN:
-                    op, literal = ALL
+        op, literal = rewrite_i64_float_cmp(op, literal)
     if col.dtype == torch.int64:
         lit_i = int(literal)
         lit_f = float(lit_i)
@@ -578,6 +572,50 @@ def filter_cmp(col: torch.Tensor, op: str, literal, workspace=None, validity=Non
                                  lit_f, lit_i,
                                  perm.data_ptr(), cnt.data_ptr(),
                                  workspace.data_ptr(), workspace.numel()))
+    c = int(cnt.item())
+    return perm[:c], c
+
+
+def filter_expr_workspace(n: int, device="cuda") -> torch.Tensor:
+    return torch.empty(lib().gpuq_filter_expr_workspace_bytes(n),
+                       dtype=torch.uint8, device=device)
+
+
+def filter_expr(columns: dict, pred, validities: dict = None, workspace=None):
+    """Stable filter on a compound predicate (spark_amd.predicate: And / Or /
+    Not / In / Between / IsNull / IsNotNull / Cmp against a literal or another
+    column), evaluated under SQL three-valued logic in one fused pass over the
+    referenced columns. Returns (perm[:count], count): the rows for which the
+    predicate is TRUE, in input order.
+
+    columns maps name -> tensor (all of one length; only the columns the
+    predicate names are read), validities name -> validity bitmap. pred may
+    also be an already lowered (column_names, program) pair."""
+    validities = validities or {}
+    if isinstance(pred, predicate.Pred):
+        names, prog = predicate.lower(
+            pred, {k: t.dtype for k, t in columns.items()})
+    else:
+        names, prog = pred
+    any_col = next(iter(columns.values()))
+    n = any_col.numel()
+    dev = any_col.device
+    for name in names:
+        if columns[name].numel() != n:
+            raise ValueError(f"filter_expr: column {name!r} has "
+                             f"{columns[name].numel()} rows, expected {n}")
+    cols_arr = (_Col * max(len(names), 1))(
+        *[_col(columns[k], validities.get(k)) for k in names])
+    prog_arr = (_PredInsn * max(len(prog), 1))(
+        *[_PredInsn(*insn) for insn in prog])
+    if workspace is None:
+        workspace = filter_expr_workspace(n, dev)
+    perm = torch.empty(n, dtype=torch.int32, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+    _check(lib().gpuq_filter_expr(_stream(), n, cols_arr, len(names),
+                                  prog_arr, len(prog),
+                                  perm.data_ptr(), cnt.data_ptr(),
+                                  workspace.data_ptr(), workspace.numel()))
     c = int(cnt.item())
     return perm[:c], c
 
