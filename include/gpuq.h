@@ -631,6 +631,96 @@ int gpuq_unpack2_i64(void* stream, int64_t nrows, const int64_t* in,
                      int64_t a_bias, int64_t b_bias, int32_t shift,
                      int64_t* out_a, int64_t* out_b);
 
+/* ---------------------------------------------------------------- */
+/* WINDOW — the device side of WindowExec (execution/window/         */
+/* WindowExec.scala): row_number / rank / dense_rank, running and    */
+/* per-partition COUNT / SUM / MIN / MAX (the frames of              */
+/* WindowFunctionFrame.scala's UnboundedPrecedingWindowFunctionFrame */
+/* and UnboundedWindowFunctionFrame) and lag / lead                  */
+/* (FrameLessOffsetWindowFunctionFrame), as segmented scans.         */
+/* The input batch is ALREADY SORTED by (partition keys, then order  */
+/* keys) — the SortExec EnsureRequirements puts below a WindowExec;  */
+/* nothing here sorts. Partition and peer-group starts are carried   */
+/* as two bitmaps of 8 * ceil(nrows / 64) bytes, LSB-first (byte-    */
+/* compatible with the Arrow validity layout), bits at and above     */
+/* nrows zero. One call computes one window expression; a node       */
+/* computes the bitmaps once and shares them.                        */
+/* ---------------------------------------------------------------- */
+
+/* bit i of out_part_start: i == 0 or some partition key differs between rows
+ * i-1 and i. bit i of out_peer_start: the part_start bit, or some order key
+ * differs (a new peer group). keys[0..npart) are the partition columns,
+ * keys[npart..nkeys) the order columns; 0 <= npart <= nkeys <= 8, each int64
+ * or float64 with optional validity. Equality is the sort's: NULL == NULL,
+ * NULL != value, int64 exact, float64 by the sort-key encoding (so -0.0 ==
+ * 0.0 and every NaN equals every NaN). nkeys == 0 gives one partition of one
+ * peer group. Each key column is read once and never written. No workspace.
+ * nrows == 0 returns GPUQ_OK with nothing launched; nrows > 0xFFFFFFFF,
+ * nkeys / npart out of range or a dtype other than int64 / float64 return
+ * GPUQ_ERR_INVALID before anything is launched. */
+int gpuq_window_boundaries(void* stream, int64_t nrows, const gpuq_col* keys,
+                           int32_t nkeys, int32_t npart,
+                           uint64_t* out_part_start, uint64_t* out_peer_start);
+
+#define GPUQ_WIN_ROW_NUMBER 0   /* int64 out; val ignored; frame must be ROWS */
+#define GPUQ_WIN_RANK       1   /* 1 + rows of the partition before the row's peer group */
+#define GPUQ_WIN_DENSE_RANK 2   /* peer groups of the partition up to and including the row's */
+#define GPUQ_WIN_COUNT      3   /* int64 out, never NULL; val.data == NULL means COUNT(*) */
+#define GPUQ_WIN_SUM        4   /* int64 -> int64 wrapping; float64 -> float64 */
+#define GPUQ_WIN_MIN        5   /* order of the aggregate's MIN/MAX (spec ops 4-7):   */
+#define GPUQ_WIN_MAX        6   /* encode_i64 / encode_f64, NaN greatest, zero emitted as +0.0 */
+
+#define GPUQ_FRAME_ROWS      0  /* ROWS  BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW */
+#define GPUQ_FRAME_RANGE     1  /* RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW: peers share the value at the last row of their group */
+#define GPUQ_FRAME_PARTITION 2  /* UNBOUNDED PRECEDING .. UNBOUNDED FOLLOWING: every row gets the partition's value */
+
+/* workspace bytes for gpuq_window_scan / gpuq_window_shift at nrows; pure
+ * arithmetic (a few words per 2048-row tile) */
+int64_t gpuq_window_workspace_bytes(int64_t nrows);
+
+/* out[i] = op over the rows of i's frame, given the bitmaps
+ * gpuq_window_boundaries produced for the same rows. out is nrows 8-byte
+ * values: int64 for the rank ops, COUNT and int64 SUM / MIN / MAX, float64
+ * for float64 SUM / MIN / MAX.
+ * NULL rules (Sum.scala / Min / Max, as the hash aggregate states them): SUM
+ * / MIN / MAX skip NULL rows; a row's result is NULL iff its frame holds no
+ * non-NULL value, and NULL result rows hold 0. MIN / MAX of float64 return
+ * the canonical NaN for any NaN and +0.0 for either zero. A float64 SUM adds
+ * in tile order, not row order: exact while every partial sum is exactly
+ * representable, otherwise within the usual reordering error; a sum over
+ * zeros only is +0.0.
+ * out_validity_bits is (nrows + 7) / 8 bytes, spare bits of the last byte
+ * zero. It may be NULL for the rank ops, for COUNT (when given it comes out
+ * all valid) and for SUM / MIN / MAX over a column without a bitmap.
+ * RANGE and PARTITION frames run the ROWS scan and then copy, in place, the
+ * value at the last row of each peer group / partition to its rows.
+ * val (and its bitmap) and the two boundary bitmaps are read twice on the
+ * stream and never written; out must not overlap them.
+ * GPUQ_ERR_INVALID before anything is launched: nrows > 0xFFFFFFFF; a bad op
+ * or frame; a rank op (0-2) with a frame other than ROWS; a value column
+ * whose dtype is not int64 / float64; SUM / MIN / MAX with val.data == NULL
+ * (and nrows > 0: an empty column's pointer may be NULL); SUM / MIN / MAX
+ * over a column with a bitmap and no out_validity_bits; a short workspace.
+ * nrows == 0 returns GPUQ_OK with nothing launched. */
+int gpuq_window_scan(void* stream, int64_t nrows, int32_t op, int32_t frame, gpuq_col val,
+                     const uint64_t* part_start, const uint64_t* peer_start,
+                     void* out, uint8_t* out_validity_bits,
+                     void* workspace, int64_t workspace_bytes);
+
+/* LAG (offset < 0) / LEAD (offset > 0): out[i] = val[i + offset] if that row
+ * lies in i's partition (it keeps its own NULL-ness: ignoreNulls = false).
+ * Otherwise out[i] is the default (lit_f64 / lit_i64 by val.dtype) when
+ * has_default, else NULL. offset == 0 copies. NULL rows hold 0.
+ * out_validity_bits ((nrows + 7) / 8 bytes) is required; out must not overlap
+ * val. Same workspace as gpuq_window_scan. GPUQ_ERR_INVALID before anything
+ * is launched: nrows > 0xFFFFFFFF, a dtype other than int64 / float64, a
+ * short workspace, val.data or out_validity_bits NULL. nrows == 0 returns
+ * GPUQ_OK with nothing launched. */
+int gpuq_window_shift(void* stream, int64_t nrows, gpuq_col val, int64_t offset,
+                      int32_t has_default, double lit_f64, int64_t lit_i64,
+                      const uint64_t* part_start, void* out, uint8_t* out_validity_bits,
+                      void* workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

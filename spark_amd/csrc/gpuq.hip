@@ -5703,3 +5703,858 @@ extern "C" int gpuq_range_i64(void* stream, int64_t n, int64_t start,
   HIP_TRY(hipGetLastError());
   return GPUQ_OK;
 }
+
+/* ================= WINDOW (segmented scan) ================= */
+/*
+ * The device side of WindowExec (execution/window/WindowExec.scala; frames as
+ * WindowFunctionFrame.scala's UnboundedPrecedingWindowFunctionFrame and
+ * UnboundedWindowFunctionFrame evaluate them). The input is already sorted by
+ * (partition keys, order keys); nothing here sorts. Partition and peer-group
+ * starts are two bitmaps of one bit per row, and every function is a
+ * segmented scan under them:
+ *
+ *  bounds  k_win_bounds: one block per WIN_TILE rows, 8 rows per thread laid
+ *          out as in k_pred_mask, so a wave's ballot is one bitmap word.
+ *  reduce  k_win_reduce: per tile, the accumulator and non-NULL count since
+ *          the tile's last partition start, a has-boundary flag, and the
+ *          first / last set bit of both bitmaps.
+ *  carry   k_win_carry: one block walks the tile summaries forward,
+ *          WIN_CARRY_SPAN at a time with a running carry: the exclusive
+ *          segmented scan (f1,a1)+(f2,a2) = (f1|f2, f2 ? a2 : a1 op a2) and a
+ *          prefix max of the last-boundary positions. A second block, which
+ *          shares nothing with the first, walks them backward for the suffix
+ *          min of the first-boundary positions.
+ *  apply   k_win_apply: re-reads the tile, scans it seeded with the carry and
+ *          writes the ROWS-frame result and its validity bits.
+ *  spread  k_win_spread (RANGE / PARTITION frames): out[i] = out[end(i)].
+ *  rank / shift read only the bitmaps and the carried positions.
+ * Bounded phases, no lookback and no spin-wait (the filter's shape).
+ *
+ * Row (r, t) of a block is base + r * WIN_BLOCK + t: in round r wave w covers
+ * the 64 rows of tile word r * WIN_WAVES + w. The flags of a word-level scan
+ * are that word itself, so a lane finds the first lane of its segment with a
+ * clz and only the accumulator travels through shuffles; the count of
+ * non-NULL rows is a popcount of the validity ballot over the same lanes.
+ */
+typedef unsigned long long wu64;
+
+#define WIN_BLOCK 256
+#define WIN_WAVES (WIN_BLOCK / WAVE)
+#define WIN_ITEMS 8
+#define WIN_TILE (WIN_BLOCK * WIN_ITEMS)     /* 2048 rows per block */
+#define WIN_WORDS (WIN_TILE / WAVE)          /* 32 bitmap words per tile */
+#define WIN_CARRY_ITEMS 8
+#define WIN_CARRY_SPAN (WIN_BLOCK * WIN_CARRY_ITEMS)  /* tiles per carry step */
+#define WIN_MAX_KEYS 8
+
+/* scan operator */
+#define WK_NONE 0      /* positions only (ROW_NUMBER, RANK, shift) */
+#define WK_ADD_U64 1
+#define WK_ADD_F64 2
+#define WK_MIN 3       /* on the monotone u64 encodings */
+#define WK_MAX 4
+/* what a row contributes */
+#define WS_RAW 0       /* the column word (SUM) */
+#define WS_ENC_I64 1
+#define WS_ENC_F64 2
+#define WS_VALID 3     /* 1 per non-NULL row: COUNT(col) */
+#define WS_ONE 4       /* 1 per row: COUNT(*) */
+#define WS_PEER 5      /* the row's peer-start bit: DENSE_RANK */
+
+template <int KIND> DEV wu64 win_ident() { return KIND == WK_MIN ? ~0ULL : 0ULL; }
+
+template <int KIND> DEV wu64 win_op(wu64 a, wu64 b) {
+  if (KIND == WK_ADD_F64)
+    return (wu64)__double_as_longlong(__longlong_as_double((long long)a) +
+                                      __longlong_as_double((long long)b));
+  if (KIND == WK_MIN) return a < b ? a : b;
+  if (KIND == WK_MAX) return a > b ? a : b;
+  return a + b;
+}
+
+/* lanes 0..lane */
+DEV wu64 win_le_mask(int lane) { return lane == 63 ? ~0ULL : ((2ULL << lane) - 1); }
+
+/* One row's contribution. ok: the row counts as a non-NULL input. A float64
+ * SUM addend goes through 0.0 + v, so a -0.0 enters as the +0.0 the running
+ * sum would make of it anyway and the result does not depend on where the
+ * tile and word edges fall. */
+template <int KIND>
+DEV wu64 win_elem(int src, const wu64* d, const uint8_t* v, wu64 peer_word,
+                  int lane, int64_t i, bool in, bool* ok) {
+  if (KIND == WK_NONE) { *ok = false; return 0; }
+  if (src == WS_ONE) { *ok = in; return in ? 1ULL : 0ULL; }
+  if (src == WS_PEER) { *ok = in; return (peer_word >> lane) & 1; }
+  bool valid = in && bit_valid(v, i);
+  *ok = valid;
+  if (src == WS_VALID) return valid ? 1ULL : 0ULL;
+  if (!valid) return win_ident<KIND>();
+  wu64 x = d[i];
+  if (src == WS_ENC_I64) return encode_i64((int64_t)x);
+  if (src == WS_ENC_F64) return encode_f64(__longlong_as_double((long long)x));
+  if (KIND == WK_ADD_F64)
+    return (wu64)__double_as_longlong(0.0 + __longlong_as_double((long long)x));
+  return x;
+}
+
+/* inclusive scan over the lanes seg0..lane of a wave (seg0: first lane of the
+ * caller's segment, the same in every lane of that segment) */
+template <int KIND>
+DEV wu64 win_wave_scan(wu64 x, int lane, int seg0) {
+  #pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+    wu64 y = __shfl_up(x, off);
+    if (lane >= off + seg0) x = win_op<KIND>(y, x);
+  }
+  return x;
+}
+
+DEV uint32_t win_wave_max_scan(uint32_t v, int lane) {
+  #pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+    uint32_t y = __shfl_up(v, off);
+    if (lane >= off && y > v) v = y;
+  }
+  return v;
+}
+
+/* v[lane] = min over lanes lane..63 */
+DEV uint32_t win_wave_min_rscan(uint32_t v, int lane) {
+  #pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+    uint32_t y = __shfl_down(v, off);
+    if (lane + off < WAVE && y < v) v = y;
+  }
+  return v;
+}
+
+/* Called by one whole wave. tab[w], w < WIN_WORDS: the last set bit of `bits`
+ * in the tile's words before w, or prev (the last set bit before the tile)
+ * when there is none. Positions ascend, so "last" is a prefix max. */
+DEV void win_begin_table(const wu64* bits, int64_t nwords, int64_t tile,
+                         uint32_t prev, uint32_t* tab, int lane) {
+  int64_t gw = tile * WIN_WORDS + lane;
+  wu64 m = (lane < WIN_WORDS && gw < nwords) ? bits[gw] : 0;
+  uint32_t v = m ? (uint32_t)(gw * WAVE + 63 - __clzll((long long)m)) : prev;
+  v = win_wave_max_scan(v, lane);
+  uint32_t e = __shfl_up(v, 1);
+  if (lane == 0) e = prev;
+  if (lane < WIN_WORDS) tab[lane] = e;
+}
+
+/* tab[w]: the first set bit in the tile's words after w, or next (the first
+ * set bit after the tile; nrows when there is none). */
+DEV void win_end_table(const wu64* bits, int64_t nwords, int64_t tile,
+                       uint32_t next, uint32_t* tab, int lane) {
+  int64_t gw = tile * WIN_WORDS + lane;
+  wu64 m = (lane < WIN_WORDS && gw < nwords) ? bits[gw] : 0;
+  uint32_t v = m ? (uint32_t)(gw * WAVE + __ffsll((long long)m) - 1) : next;
+  v = win_wave_min_rscan(v, lane);
+  uint32_t e = __shfl_down(v, 1);   /* lane 31 reads lane 32, which holds next */
+  if (lane < WIN_WORDS) tab[lane] = e;
+}
+
+/* last set bit of word m at or before `lane`, as a row position; tab_w when
+ * the word has none there */
+DEV uint32_t win_begin_of(wu64 m, int lane, int64_t word_base, uint32_t tab_w) {
+  wu64 le = m & win_le_mask(lane);
+  return le ? (uint32_t)(word_base + 63 - __clzll((long long)le)) : tab_w;
+}
+
+/* last row of the group that holds `lane`: the next set bit after it, minus 1 */
+DEV uint32_t win_end_of(wu64 m, int lane, int64_t word_base, uint32_t tab_w,
+                        int64_t n) {
+  wu64 gt = m & ~win_le_mask(lane);
+  uint32_t nb = gt ? (uint32_t)(word_base + __ffsll((long long)gt) - 1) : tab_w;
+  if (nb > n) nb = (uint32_t)n;   /* a bitmap with bits past nrows reads nothing there */
+  return nb - 1;
+}
+
+/* validity bits of 64 consecutive rows from their ballot: lanes 0..7 store
+ * one byte each; bytes past the bitmap's (nrows + 7) / 8 are not touched */
+DEV void win_store_valid(uint8_t* bits, int64_t nbytes, int64_t gw, wu64 m, int lane) {
+  if (bits && lane < 8) {
+    int64_t b = gw * 8 + lane;
+    if (b < nbytes) bits[b] = (uint8_t)(m >> (8 * lane));
+  }
+}
+
+struct win_keys {
+  const wu64* data[WIN_MAX_KEYS];
+  const uint8_t* validity[WIN_MAX_KEYS];
+  int32_t dtype[WIN_MAX_KEYS];
+  int32_t nkeys, npart;
+};
+
+/* Each row compares itself with row i-1 in every key column. The neighbour
+ * comes from the lane below; lane 0 of a wave loads it (the same line the
+ * wave before it streams). Equality is the sort's: both NULL, or both valid
+ * with equal encodings (encode_f64: -0.0 == 0.0, one NaN). */
+__global__ __launch_bounds__(WIN_BLOCK)
+void k_win_bounds(int64_t n, win_keys k, wu64* part, wu64* peer) {
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  const int64_t base = (int64_t)blockIdx.x * WIN_TILE + threadIdx.x;
+  uint32_t pd = 0, od = 0;   /* bit r: row r differs from its predecessor */
+  for (int c = 0; c < k.nkeys; c++) {
+    const wu64* d = k.data[c];
+    const uint8_t* v = k.validity[c];
+    const bool f64 = k.dtype[c] == GPUQ_FLOAT64;
+    uint32_t diff = 0;
+    #pragma unroll
+    for (int r = 0; r < WIN_ITEMS; r++) {
+      const int64_t i = base + r * WIN_BLOCK;
+      const bool in = i < n;
+      wu64 cur = in ? d[i] : 0;
+      if (f64) cur = encode_f64(__longlong_as_double((long long)cur));
+      int cv = in && bit_valid(v, i);
+      wu64 prev = __shfl_up(cur, 1);
+      int pv = __shfl_up(cv, 1);
+      if (lane == 0 && in && i > 0) {
+        prev = d[i - 1];
+        if (f64) prev = encode_f64(__longlong_as_double((long long)prev));
+        pv = bit_valid(v, i - 1);
+      }
+      bool ne = cv != pv || (cv && cur != prev);
+      diff |= (uint32_t)(in && ne) << r;
+    }
+    if (c < k.npart) pd |= diff; else od |= diff;
+  }
+  const int64_t nwords = (n + WAVE - 1) / WAVE;
+  #pragma unroll
+  for (int r = 0; r < WIN_ITEMS; r++) {
+    const int64_t i = base + r * WIN_BLOCK;
+    bool p = i < n && (i == 0 || ((pd >> r) & 1));
+    bool q = i < n && (p || ((od >> r) & 1));
+    wu64 mp = __ballot(p), mq = __ballot(q);
+    int64_t gw = (int64_t)blockIdx.x * WIN_WORDS + r * WIN_WAVES + wave;
+    if (lane == 0 && gw < nwords) { part[gw] = mp; peer[gw] = mq; }
+  }
+}
+
+/* per-tile summaries (reduce) and carries (carry), one entry per tile */
+struct win_ws {
+  wu64* sum_acc;        /* accumulator since the tile's last partition start */
+  wu64* car_acc;        /* accumulator carried INTO the tile */
+  uint32_t* sum_cnt;    /* non-NULL rows since the tile's last partition start */
+  uint32_t* sum_flag;   /* the tile holds a partition start */
+  uint32_t* first_part; /* first / last set bit of the tile, nrows / 0 if none */
+  uint32_t* last_part;
+  uint32_t* first_peer;
+  uint32_t* last_peer;
+  uint32_t* car_cnt;
+  uint32_t* prev_part;  /* last set bit before the tile */
+  uint32_t* prev_peer;
+  uint32_t* next_part;  /* first set bit after the tile, nrows if none */
+  uint32_t* next_peer;
+};
+
+static void win_ws_layout(int64_t n, win_ws* w, char* basep, int64_t* total) {
+  int64_t nt = (n + WIN_TILE - 1) / WIN_TILE;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) {
+    char* p = basep ? basep + off : nullptr;
+    off += (bytes + 255) & ~255LL;
+    return p;
+  };
+  w->sum_acc = (wu64*)take(nt * 8);
+  w->car_acc = (wu64*)take(nt * 8);
+  uint32_t** u32s[] = {&w->sum_cnt, &w->sum_flag, &w->first_part, &w->last_part,
+                       &w->first_peer, &w->last_peer, &w->car_cnt, &w->prev_part,
+                       &w->prev_peer, &w->next_part, &w->next_peer};
+  for (auto p : u32s) *p = (uint32_t*)take(nt * 4);
+  *total = off;
+}
+
+extern "C" int64_t gpuq_window_workspace_bytes(int64_t n) {
+  if (n < 0) n = 0;
+  win_ws w; int64_t total;
+  win_ws_layout(n, &w, nullptr, &total);
+  return total;
+}
+
+/* Wave 0 finds the first / last set bit of both bitmaps in the tile; then
+ * (KIND != WK_NONE) every row at or after the last partition start — every
+ * row of the tile when it has none — is folded into the tile's accumulator.
+ * A missing first bit is stored as nrows and a missing last bit as 0 (row 0
+ * starts a partition and a peer group, so 0 is the carry's neutral value). */
+template <int KIND>
+__global__ __launch_bounds__(WIN_BLOCK)
+void k_win_reduce(int64_t n, int src, const wu64* d, const uint8_t* v,
+                  const wu64* part, const wu64* peer, win_ws w) {
+  __shared__ int s_last;             /* tile-relative, -1: no partition start */
+  __shared__ wu64 s_acc[WIN_WAVES];
+  __shared__ uint32_t s_cnt[WIN_WAVES];
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  const int64_t tile = blockIdx.x;
+  const int64_t nwords = (n + WAVE - 1) / WAVE;
+  if (wave == 0) {
+    int64_t gw = tile * WIN_WORDS + lane;
+    bool have = lane < WIN_WORDS && gw < nwords;
+    wu64 mp = have ? part[gw] : 0, mq = have ? peer[gw] : 0;
+    wu64 bp = __ballot(mp != 0), bq = __ballot(mq != 0);
+    int wlp = bp ? 63 - __clzll((long long)bp) : 0, wfp = bp ? __ffsll((long long)bp) - 1 : 0;
+    int wlq = bq ? 63 - __clzll((long long)bq) : 0, wfq = bq ? __ffsll((long long)bq) - 1 : 0;
+    wu64 lpw = __shfl(mp, wlp), fpw = __shfl(mp, wfp);
+    wu64 lqw = __shfl(mq, wlq), fqw = __shfl(mq, wfq);
+    if (lane == 0) {
+      const int64_t tb = tile * WIN_TILE;
+      int lastrel = bp ? wlp * WAVE + 63 - __clzll((long long)lpw) : -1;
+      s_last = lastrel;
+      w.sum_flag[tile] = bp != 0;
+      w.last_part[tile] = bp ? (uint32_t)(tb + lastrel) : 0u;
+      w.first_part[tile] = bp ? (uint32_t)(tb + wfp * WAVE + __ffsll((long long)fpw) - 1)
+                              : (uint32_t)n;
+      w.last_peer[tile] = bq ? (uint32_t)(tb + wlq * WAVE + 63 - __clzll((long long)lqw)) : 0u;
+      w.first_peer[tile] = bq ? (uint32_t)(tb + wfq * WAVE + __ffsll((long long)fqw) - 1)
+                              : (uint32_t)n;
+    }
+  }
+  if (KIND == WK_NONE) return;
+  /* the rows are loaded before the barrier, so the loads do not wait for
+   * wave 0's bitmap words */
+  wu64 x[WIN_ITEMS];
+  uint32_t okb = 0;
+  #pragma unroll
+  for (int r = 0; r < WIN_ITEMS; r++) {
+    const int64_t gw = tile * WIN_WORDS + r * WIN_WAVES + wave;
+    const int64_t i = gw * WAVE + lane;
+    wu64 pw = (src == WS_PEER && gw < nwords) ? peer[gw] : 0;
+    bool ok;
+    x[r] = win_elem<KIND>(src, d, v, pw, lane, i, i < n, &ok);
+    okb |= (uint32_t)ok << r;
+  }
+  __syncthreads();
+  const int lastrel = s_last;
+  wu64 acc = win_ident<KIND>();
+  uint32_t cnt = 0;
+  #pragma unroll
+  for (int r = 0; r < WIN_ITEMS; r++) {
+    if ((r * WIN_WAVES + wave) * WAVE + lane >= lastrel) {
+      acc = win_op<KIND>(acc, x[r]);
+      cnt += (okb >> r) & 1;
+    }
+  }
+  #pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    acc = win_op<KIND>(acc, __shfl_down(acc, off));
+    cnt += __shfl_down(cnt, off);
+  }
+  if (lane == 0) { s_acc[wave] = acc; s_cnt[wave] = cnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    #pragma unroll
+    for (int k = 1; k < WIN_WAVES; k++) {
+      acc = win_op<KIND>(acc, s_acc[k]);
+      cnt += s_cnt[k];
+    }
+    w.sum_acc[tile] = acc;
+    w.sum_cnt[tile] = cnt;
+  }
+}
+
+/* Two blocks that never talk to each other: block 0 walks the tiles forward,
+ * block 1 backward. Forward: thread t of a step owns WIN_CARRY_ITEMS
+ * consecutive tiles; it folds them, the block scans the 256 thread totals
+ * (wave scan with the flag ballot, then the 4 wave totals in order), and the
+ * thread walks its tiles again writing the value carried INTO each. `run` is
+ * the carry out of the previous step, recomputed identically by every
+ * thread. Backward: the same walk from the last tile for the suffix min of
+ * the first-boundary positions. ntiles <= 2^21, so at most 1024 steps. */
+template <int KIND>
+__global__ __launch_bounds__(WIN_BLOCK)
+void k_win_carry(int64_t ntiles, uint32_t n, win_ws w) {
+  __shared__ wu64 s_acc[WIN_WAVES];
+  __shared__ uint32_t s_cnt[WIN_WAVES], s_flag[WIN_WAVES], s_pp[WIN_WAVES], s_pq[WIN_WAVES];
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  wu64 run_acc = win_ident<KIND>();
+  uint32_t run_cnt = 0, run_pp = 0, run_pq = 0;
+  for (int64_t base = 0; blockIdx.x == 0 && base < ntiles; base += WIN_CARRY_SPAN) {
+    const int64_t t0 = base + (int64_t)threadIdx.x * WIN_CARRY_ITEMS;
+    /* this thread's tiles, loaded back to back (tiles past the end are
+     * neutral), then folded: (f, a, c) and the last boundary positions */
+    uint32_t tf[WIN_CARRY_ITEMS], tc[WIN_CARRY_ITEMS], tlp[WIN_CARRY_ITEMS],
+        tlq[WIN_CARRY_ITEMS];
+    wu64 ta[WIN_CARRY_ITEMS];
+    #pragma unroll
+    for (int k = 0; k < WIN_CARRY_ITEMS; k++) {
+      const int64_t t = t0 + k;
+      const bool have = t < ntiles;
+      tf[k] = (KIND != WK_NONE && have) ? w.sum_flag[t] : 0;
+      ta[k] = (KIND != WK_NONE && have) ? w.sum_acc[t] : win_ident<KIND>();
+      tc[k] = (KIND != WK_NONE && have) ? w.sum_cnt[t] : 0;
+      tlp[k] = have ? w.last_part[t] : 0;
+      tlq[k] = have ? w.last_peer[t] : 0;
+    }
+    uint32_t f = 0, c = 0, pp = 0, pq = 0;
+    wu64 a = win_ident<KIND>();
+    #pragma unroll
+    for (int k = 0; k < WIN_CARRY_ITEMS; k++) {
+      if (KIND != WK_NONE) {
+        if (tf[k]) { f = 1; a = ta[k]; c = tc[k]; }
+        else { a = win_op<KIND>(a, ta[k]); c += tc[k]; }
+      }
+      pp = tlp[k] > pp ? tlp[k] : pp;
+      pq = tlq[k] > pq ? tlq[k] : pq;
+    }
+    /* inclusive scan across the wave */
+    const wu64 fm = __ballot(f != 0);
+    const wu64 fle = fm & win_le_mask(lane);
+    const int seg0 = fle ? 63 - __clzll((long long)fle) : 0;
+    wu64 ia = a;
+    uint32_t ic = c;
+    if (KIND != WK_NONE) {
+      ia = win_wave_scan<KIND>(a, lane, seg0);
+      #pragma unroll
+      for (int off = 1; off < WAVE; off <<= 1) {
+        uint32_t y = __shfl_up(ic, off);
+        if (lane >= off + seg0) ic += y;
+      }
+    }
+    const uint32_t ipp = win_wave_max_scan(pp, lane), ipq = win_wave_max_scan(pq, lane);
+    if (lane == WAVE - 1) {
+      s_acc[wave] = ia; s_cnt[wave] = ic; s_flag[wave] = fm != 0;
+      s_pp[wave] = ipp; s_pq[wave] = ipq;
+    }
+    __syncthreads();
+    /* carry into this wave, and (same loop, run to the end) out of the step */
+    wu64 wa = run_acc;
+    uint32_t wc = run_cnt, wpp = run_pp, wpq = run_pq;
+    wu64 in_a = wa;
+    uint32_t in_c = wc, in_pp = wpp, in_pq = wpq;
+    #pragma unroll
+    for (int k = 0; k < WIN_WAVES; k++) {
+      if (k == wave) { in_a = wa; in_c = wc; in_pp = wpp; in_pq = wpq; }
+      if (KIND != WK_NONE) {
+        if (s_flag[k]) { wa = s_acc[k]; wc = s_cnt[k]; }
+        else { wa = win_op<KIND>(wa, s_acc[k]); wc += s_cnt[k]; }
+      }
+      wpp = s_pp[k] > wpp ? s_pp[k] : wpp;
+      wpq = s_pq[k] > wpq ? s_pq[k] : wpq;
+    }
+    run_acc = wa; run_cnt = wc; run_pp = wpp; run_pq = wpq;
+    /* exclusive value of this thread: the lane below, under the wave carry */
+    wu64 ea = __shfl_up(ia, 1);
+    uint32_t ec = __shfl_up(ic, 1);
+    uint32_t epp = __shfl_up(ipp, 1), epq = __shfl_up(ipq, 1);
+    const bool flag_below = (fm & (win_le_mask(lane) >> 1)) != 0;
+    if (lane == 0) { ea = in_a; ec = in_c; epp = in_pp; epq = in_pq; }
+    else {
+      if (KIND != WK_NONE && !flag_below) { ea = win_op<KIND>(in_a, ea); ec += in_c; }
+      epp = in_pp > epp ? in_pp : epp;
+      epq = in_pq > epq ? in_pq : epq;
+    }
+    #pragma unroll
+    for (int k = 0; k < WIN_CARRY_ITEMS; k++) {
+      const int64_t t = t0 + k;
+      if (t < ntiles) {
+        w.prev_part[t] = epp;
+        w.prev_peer[t] = epq;
+        epp = tlp[k] > epp ? tlp[k] : epp;
+        epq = tlq[k] > epq ? tlq[k] : epq;
+        if (KIND != WK_NONE) {
+          w.car_acc[t] = ea;
+          w.car_cnt[t] = ec;
+          if (tf[k]) { ea = ta[k]; ec = tc[k]; }
+          else { ea = win_op<KIND>(ea, ta[k]); ec += tc[k]; }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  /* suffix min of the first-boundary positions: tile u counts from the end */
+  uint32_t run_np = n, run_nq = n;
+  for (int64_t base = 0; blockIdx.x == 1 && base < ntiles; base += WIN_CARRY_SPAN) {
+    const int64_t u0 = base + (int64_t)threadIdx.x * WIN_CARRY_ITEMS;
+    uint32_t tfp[WIN_CARRY_ITEMS], tfq[WIN_CARRY_ITEMS];
+    #pragma unroll
+    for (int k = 0; k < WIN_CARRY_ITEMS; k++) {
+      const int64_t u = u0 + k;
+      tfp[k] = u < ntiles ? w.first_part[ntiles - 1 - u] : n;
+      tfq[k] = u < ntiles ? w.first_peer[ntiles - 1 - u] : n;
+    }
+    uint32_t np = n, nq = n;
+    #pragma unroll
+    for (int k = 0; k < WIN_CARRY_ITEMS; k++) {
+      np = tfp[k] < np ? tfp[k] : np;
+      nq = tfq[k] < nq ? tfq[k] : nq;
+    }
+    /* prefix min in u order == suffix min in tile order */
+    uint32_t inp = np, inq = nq;
+    #pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+      uint32_t y = __shfl_up(inp, off), z = __shfl_up(inq, off);
+      if (lane >= off) { inp = y < inp ? y : inp; inq = z < inq ? z : inq; }
+    }
+    if (lane == WAVE - 1) { s_pp[wave] = inp; s_pq[wave] = inq; }
+    __syncthreads();
+    uint32_t wnp = run_np, wnq = run_nq, in_np = run_np, in_nq = run_nq;
+    #pragma unroll
+    for (int k = 0; k < WIN_WAVES; k++) {
+      if (k == wave) { in_np = wnp; in_nq = wnq; }
+      wnp = s_pp[k] < wnp ? s_pp[k] : wnp;
+      wnq = s_pq[k] < wnq ? s_pq[k] : wnq;
+    }
+    run_np = wnp; run_nq = wnq;
+    uint32_t enp = __shfl_up(inp, 1), enq = __shfl_up(inq, 1);
+    if (lane == 0) { enp = in_np; enq = in_nq; }
+    else { enp = in_np < enp ? in_np : enp; enq = in_nq < enq ? in_nq : enq; }
+    #pragma unroll
+    for (int k = 0; k < WIN_CARRY_ITEMS; k++) {
+      const int64_t u = u0 + k;
+      if (u < ntiles) {
+        const int64_t t = ntiles - 1 - u;
+        w.next_part[t] = enp;
+        w.next_peer[t] = enq;
+        enp = tfp[k] < enp ? tfp[k] : enp;
+        enq = tfq[k] < enq ? tfq[k] : enq;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+/* The ROWS-frame result of every row of the tile. Word scans in registers,
+ * their 32 totals scanned by wave 0 under the tile's carry, then each row
+ * whose word has no partition start at or before it takes its word's carry.
+ * dec: 0 raw word, 1 decode_i64, 2 decode_f64. A row with no non-NULL value
+ * in its frame is NULL and holds 0, unless never_null (COUNT, DENSE_RANK). */
+template <int KIND>
+__global__ __launch_bounds__(WIN_BLOCK)
+void k_win_apply(int64_t n, int src, const wu64* d, const uint8_t* v,
+                 const wu64* part, const wu64* peer, win_ws w, int dec,
+                 int never_null, wu64* out, uint8_t* out_valid, int64_t nbytes) {
+  __shared__ wu64 s_acc[WIN_WORDS], s_xacc[WIN_WORDS];
+  __shared__ uint32_t s_cnt[WIN_WORDS], s_xcnt[WIN_WORDS], s_flag[WIN_WORDS];
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  const int64_t tile = blockIdx.x;
+  const int64_t nwords = (n + WAVE - 1) / WAVE;
+  wu64 x[WIN_ITEMS];
+  uint32_t c[WIN_ITEMS];
+  uint32_t started = 0;   /* bit r: a partition starts at or before this lane in word r */
+  #pragma unroll
+  for (int r = 0; r < WIN_ITEMS; r++) {
+    const int wd = r * WIN_WAVES + wave;
+    const int64_t gw = tile * WIN_WORDS + wd;
+    const int64_t i = gw * WAVE + lane;
+    const wu64 m = gw < nwords ? part[gw] : 0;
+    const wu64 pw = (src == WS_PEER && gw < nwords) ? peer[gw] : 0;
+    bool ok;
+    wu64 e = win_elem<KIND>(src, d, v, pw, lane, i, i < n, &ok);
+    const wu64 vm = __ballot(ok);
+    const wu64 le = win_le_mask(lane);
+    const wu64 mle = m & le;
+    const int seg0 = mle ? 63 - __clzll((long long)mle) : 0;
+    x[r] = win_wave_scan<KIND>(e, lane, seg0);
+    c[r] = (uint32_t)__popcll(vm & le & ~((1ULL << seg0) - 1));
+    started |= (uint32_t)(mle != 0) << r;
+    if (lane == WAVE - 1) { s_acc[wd] = x[r]; s_cnt[wd] = c[r]; s_flag[wd] = m != 0; }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const wu64 tc_acc = w.car_acc[tile];
+    const uint32_t tc_cnt = w.car_cnt[tile];
+    wu64 a = lane < WIN_WORDS ? s_acc[lane] : win_ident<KIND>();
+    uint32_t cn = lane < WIN_WORDS ? s_cnt[lane] : 0;
+    const wu64 fm = __ballot(lane < WIN_WORDS && s_flag[lane] != 0);
+    const wu64 fle = fm & win_le_mask(lane);
+    const int seg0 = fle ? 63 - __clzll((long long)fle) : 0;
+    a = win_wave_scan<KIND>(a, lane, seg0);
+    #pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+      uint32_t y = __shfl_up(cn, off);
+      if (lane >= off + seg0) cn += y;
+    }
+    if (!fle) { a = win_op<KIND>(tc_acc, a); cn += tc_cnt; }
+    /* the value carried into word lane + 1 */
+    if (lane < WIN_WORDS - 1) { s_xacc[lane + 1] = a; s_xcnt[lane + 1] = cn; }
+    if (lane == 0) { s_xacc[0] = tc_acc; s_xcnt[0] = tc_cnt; }
+  }
+  __syncthreads();
+  #pragma unroll
+  for (int r = 0; r < WIN_ITEMS; r++) {
+    const int wd = r * WIN_WAVES + wave;
+    const int64_t gw = tile * WIN_WORDS + wd;
+    const int64_t i = gw * WAVE + lane;
+    wu64 a = x[r];
+    uint32_t cn = c[r];
+    if (!((started >> r) & 1)) { a = win_op<KIND>(s_xacc[wd], a); cn += s_xcnt[wd]; }
+    const bool valid = i < n && (never_null || cn > 0);
+    if (i < n) {
+      wu64 o = 0;
+      if (valid)
+        o = dec == 1 ? (wu64)decode_i64(a)
+          : dec == 2 ? (wu64)__double_as_longlong(decode_f64(a)) : a;
+      out[i] = o;
+    }
+    win_store_valid(out_valid, nbytes, gw, __ballot(valid), lane);
+  }
+}
+
+/* out[i] = out[end(i)], end(i) the last row of i's group under `bits` (peer
+ * starts for RANGE, partition starts for PARTITION), and the same for the
+ * validity bit. In place: end(end(i)) == end(i), so a row that others read is
+ * rewritten with the value and the bit it already holds. */
+__global__ __launch_bounds__(WIN_BLOCK)
+void k_win_spread(int64_t n, const wu64* bits, const uint32_t* next,
+                  wu64* out, uint8_t* out_valid, int64_t nbytes) {
+  __shared__ uint32_t s_end[WIN_WORDS];
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  const int64_t tile = blockIdx.x;
+  const int64_t nwords = (n + WAVE - 1) / WAVE;
+  if (wave == 0) win_end_table(bits, nwords, tile, next[tile], s_end, lane);
+  __syncthreads();
+  #pragma unroll
+  for (int r = 0; r < WIN_ITEMS; r++) {
+    const int wd = r * WIN_WAVES + wave;
+    const int64_t gw = tile * WIN_WORDS + wd;
+    const int64_t i = gw * WAVE + lane;
+    bool valid = false;
+    if (i < n) {
+      const uint32_t e = win_end_of(bits[gw], lane, gw * WAVE, s_end[wd], n);
+      valid = bit_valid(out_valid, e);
+      out[i] = out[e];
+    }
+    win_store_valid(out_valid, nbytes, gw, __ballot(valid), lane);
+  }
+}
+
+/* ROW_NUMBER = i - part_begin(i) + 1, RANK = peer_begin(i) - part_begin(i) + 1 */
+__global__ __launch_bounds__(WIN_BLOCK)
+void k_win_rank(int64_t n, int op, const wu64* part, const wu64* peer,
+                const uint32_t* prev_part, const uint32_t* prev_peer, int64_t* out,
+                uint8_t* out_valid, int64_t nbytes) {
+  __shared__ uint32_t s_pb[WIN_WORDS], s_qb[WIN_WORDS];
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  const int64_t tile = blockIdx.x;
+  const int64_t nwords = (n + WAVE - 1) / WAVE;
+  if (wave == 0) win_begin_table(part, nwords, tile, prev_part[tile], s_pb, lane);
+  if (wave == 1) win_begin_table(peer, nwords, tile, prev_peer[tile], s_qb, lane);
+  __syncthreads();
+  #pragma unroll
+  for (int r = 0; r < WIN_ITEMS; r++) {
+    const int wd = r * WIN_WAVES + wave;
+    const int64_t gw = tile * WIN_WORDS + wd;
+    const int64_t i = gw * WAVE + lane;
+    if (i < n) {
+      const int64_t pb = win_begin_of(part[gw], lane, gw * WAVE, s_pb[wd]);
+      const int64_t top = op == GPUQ_WIN_RANK
+          ? (int64_t)win_begin_of(peer[gw], lane, gw * WAVE, s_qb[wd]) : i;
+      out[i] = top - pb + 1;
+    }
+    win_store_valid(out_valid, nbytes, gw, __ballot(i < n), lane);
+  }
+}
+
+/* out[i] = val[i + offset] when that row lies in i's partition */
+__global__ __launch_bounds__(WIN_BLOCK)
+void k_win_shift(int64_t n, const wu64* d, const uint8_t* v, int64_t offset,
+                 int has_default, wu64 dflt, const wu64* part,
+                 const uint32_t* prev_part, const uint32_t* next_part,
+                 wu64* out, uint8_t* out_valid, int64_t nbytes) {
+  __shared__ uint32_t s_pb[WIN_WORDS], s_pe[WIN_WORDS];
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  const int64_t tile = blockIdx.x;
+  const int64_t nwords = (n + WAVE - 1) / WAVE;
+  if (wave == 0) win_begin_table(part, nwords, tile, prev_part[tile], s_pb, lane);
+  if (wave == 1) win_end_table(part, nwords, tile, next_part[tile], s_pe, lane);
+  __syncthreads();
+  #pragma unroll
+  for (int r = 0; r < WIN_ITEMS; r++) {
+    const int wd = r * WIN_WAVES + wave;
+    const int64_t gw = tile * WIN_WORDS + wd;
+    const int64_t i = gw * WAVE + lane;
+    bool valid = false;
+    if (i < n) {
+      const wu64 m = part[gw];
+      const int64_t j = i + offset;
+      const bool inpart = offset < 0
+          ? j >= (int64_t)win_begin_of(m, lane, gw * WAVE, s_pb[wd])
+          : j <= (int64_t)win_end_of(m, lane, gw * WAVE, s_pe[wd], n);
+      wu64 x = 0;
+      if (inpart) {
+        valid = bit_valid(v, j);
+        if (valid) x = d[j];
+      } else if (has_default) {
+        valid = true;
+        x = dflt;
+      }
+      out[i] = x;
+    }
+    win_store_valid(out_valid, nbytes, gw, __ballot(valid), lane);
+  }
+}
+
+extern "C" int gpuq_window_boundaries(void* stream, int64_t n, const gpuq_col* keys,
+                                      int32_t nkeys, int32_t npart,
+                                      uint64_t* out_part_start,
+                                      uint64_t* out_peer_start) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 0 || n > 0xFFFFFFFFLL)
+    FAIL(GPUQ_ERR_INVALID, "window_boundaries: nrows %lld out of range", (long long)n);
+  if (nkeys < 0 || nkeys > WIN_MAX_KEYS)
+    FAIL(GPUQ_ERR_INVALID, "window_boundaries: %d keys, need 0..%d", nkeys, WIN_MAX_KEYS);
+  if (npart < 0 || npart > nkeys)
+    FAIL(GPUQ_ERR_INVALID, "window_boundaries: %d partition keys of %d keys", npart, nkeys);
+  win_keys k;
+  memset(&k, 0, sizeof(k));
+  for (int c = 0; c < nkeys; c++) {
+    if (keys[c].dtype != GPUQ_INT64 && keys[c].dtype != GPUQ_FLOAT64)
+      FAIL(GPUQ_ERR_INVALID, "window_boundaries: key %d has unsupported dtype %d", c, keys[c].dtype);
+    k.data[c] = (const wu64*)keys[c].data;
+    k.validity[c] = keys[c].validity;
+    k.dtype[c] = keys[c].dtype;
+  }
+  k.nkeys = nkeys; k.npart = npart;
+  if (n == 0) return GPUQ_OK;
+  const int64_t nt = (n + WIN_TILE - 1) / WIN_TILE;
+  { hipEvent_t _pe = prof_begin(s);
+  k_win_bounds<<<dim3((uint32_t)nt), WIN_BLOCK, 0, s>>>(
+      n, k, (wu64*)out_part_start, (wu64*)out_peer_start);
+  prof_end("win_bounds", s, _pe); }
+  HIP_TRY(hipGetLastError());
+  return GPUQ_OK;
+}
+
+/* reduce + carry for one scan operator */
+template <int KIND>
+static void win_reduce_carry(hipStream_t s, int64_t n, int src, gpuq_col val,
+                             const uint64_t* part, const uint64_t* peer, win_ws& w) {
+  const int64_t nt = (n + WIN_TILE - 1) / WIN_TILE;
+  { hipEvent_t _pe = prof_begin(s);
+  k_win_reduce<KIND><<<dim3((uint32_t)nt), WIN_BLOCK, 0, s>>>(
+      n, src, (const wu64*)val.data, val.validity, (const wu64*)part,
+      (const wu64*)peer, w);
+  prof_end("win_reduce", s, _pe); }
+  { hipEvent_t _pe = prof_begin(s);
+  k_win_carry<KIND><<<2, WIN_BLOCK, 0, s>>>(nt, (uint32_t)n, w);
+  prof_end("win_carry", s, _pe); }
+}
+
+template <int KIND>
+static void win_scan_rows(hipStream_t s, int64_t n, int src, gpuq_col val,
+                          const uint64_t* part, const uint64_t* peer, win_ws& w,
+                          int dec, int never_null, void* out, uint8_t* out_valid) {
+  const int64_t nt = (n + WIN_TILE - 1) / WIN_TILE;
+  win_reduce_carry<KIND>(s, n, src, val, part, peer, w);
+  { hipEvent_t _pe = prof_begin(s);
+  k_win_apply<KIND><<<dim3((uint32_t)nt), WIN_BLOCK, 0, s>>>(
+      n, src, (const wu64*)val.data, val.validity, (const wu64*)part,
+      (const wu64*)peer, w, dec, never_null, (wu64*)out, out_valid, (n + 7) / 8);
+  prof_end("win_apply", s, _pe); }
+}
+
+extern "C" int gpuq_window_scan(void* stream, int64_t n, int32_t op, int32_t frame,
+                                gpuq_col val, const uint64_t* part_start,
+                                const uint64_t* peer_start, void* out,
+                                uint8_t* out_validity_bits,
+                                void* workspace, int64_t workspace_bytes) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 0 || n > 0xFFFFFFFFLL)
+    FAIL(GPUQ_ERR_INVALID, "window_scan: nrows %lld out of range", (long long)n);
+  if (op < GPUQ_WIN_ROW_NUMBER || op > GPUQ_WIN_MAX)
+    FAIL(GPUQ_ERR_INVALID, "window_scan: bad op %d", op);
+  if (frame < GPUQ_FRAME_ROWS || frame > GPUQ_FRAME_PARTITION)
+    FAIL(GPUQ_ERR_INVALID, "window_scan: bad frame %d", frame);
+  const bool rank_op = op <= GPUQ_WIN_DENSE_RANK;
+  if (rank_op && frame != GPUQ_FRAME_ROWS)
+    FAIL(GPUQ_ERR_INVALID, "window_scan: rank op %d takes the ROWS frame only", op);
+  const bool reads_val = !rank_op && (op != GPUQ_WIN_COUNT || val.data);
+  /* an empty column's pointer may be NULL */
+  if (n > 0 && !rank_op && op != GPUQ_WIN_COUNT && !val.data)
+    FAIL(GPUQ_ERR_INVALID, "window_scan: op %d needs a value column", op);
+  if (reads_val && val.dtype != GPUQ_INT64 && val.dtype != GPUQ_FLOAT64)
+    FAIL(GPUQ_ERR_INVALID, "window_scan: unsupported dtype %d", val.dtype);
+  const bool never_null = rank_op || op == GPUQ_WIN_COUNT;
+  if (!never_null && val.validity && !out_validity_bits)
+    FAIL(GPUQ_ERR_INVALID, "window_scan: a nullable value column needs an output bitmap");
+  win_ws w; int64_t need;
+  win_ws_layout(n, &w, (char*)workspace, &need);
+  if (workspace_bytes < need)
+    FAIL(GPUQ_ERR_INVALID, "window_scan: workspace %lld < %lld",
+         (long long)workspace_bytes, (long long)need);
+  if (n == 0) return GPUQ_OK;
+  const int64_t nt = (n + WIN_TILE - 1) / WIN_TILE;
+  const bool f64 = val.dtype == GPUQ_FLOAT64;
+  if (!reads_val) val.validity = nullptr;
+  switch (op) {
+    case GPUQ_WIN_ROW_NUMBER:
+    case GPUQ_WIN_RANK:
+      win_reduce_carry<WK_NONE>(s, n, WS_ONE, val, part_start, peer_start, w);
+      { hipEvent_t _pe = prof_begin(s);
+      k_win_rank<<<dim3((uint32_t)nt), WIN_BLOCK, 0, s>>>(
+          n, op, (const wu64*)part_start, (const wu64*)peer_start,
+          w.prev_part, w.prev_peer, (int64_t*)out, out_validity_bits, (n + 7) / 8);
+      prof_end("win_apply", s, _pe); }
+      break;
+    case GPUQ_WIN_DENSE_RANK:
+      win_scan_rows<WK_ADD_U64>(s, n, WS_PEER, val, part_start, peer_start, w, 0, 1,
+                                out, out_validity_bits);
+      break;
+    case GPUQ_WIN_COUNT:
+      win_scan_rows<WK_ADD_U64>(s, n, val.data ? WS_VALID : WS_ONE, val, part_start,
+                                peer_start, w, 0, 1, out, out_validity_bits);
+      break;
+    case GPUQ_WIN_SUM:
+      if (f64) win_scan_rows<WK_ADD_F64>(s, n, WS_RAW, val, part_start, peer_start, w,
+                                         0, 0, out, out_validity_bits);
+      else win_scan_rows<WK_ADD_U64>(s, n, WS_RAW, val, part_start, peer_start, w,
+                                     0, 0, out, out_validity_bits);
+      break;
+    case GPUQ_WIN_MIN:
+      win_scan_rows<WK_MIN>(s, n, f64 ? WS_ENC_F64 : WS_ENC_I64, val, part_start,
+                            peer_start, w, f64 ? 2 : 1, 0, out, out_validity_bits);
+      break;
+    default:
+      win_scan_rows<WK_MAX>(s, n, f64 ? WS_ENC_F64 : WS_ENC_I64, val, part_start,
+                            peer_start, w, f64 ? 2 : 1, 0, out, out_validity_bits);
+      break;
+  }
+  HIP_TRY(hipGetLastError());
+  if (frame != GPUQ_FRAME_ROWS) {
+    const bool range = frame == GPUQ_FRAME_RANGE;
+    { hipEvent_t _pe = prof_begin(s);
+    k_win_spread<<<dim3((uint32_t)nt), WIN_BLOCK, 0, s>>>(
+        n, (const wu64*)(range ? peer_start : part_start),
+        range ? w.next_peer : w.next_part, (wu64*)out, out_validity_bits, (n + 7) / 8);
+    prof_end("win_spread", s, _pe); }
+    HIP_TRY(hipGetLastError());
+  }
+  return GPUQ_OK;
+}
+
+extern "C" int gpuq_window_shift(void* stream, int64_t n, gpuq_col val, int64_t offset,
+                                 int32_t has_default, double lit_f64, int64_t lit_i64,
+                                 const uint64_t* part_start, void* out,
+                                 uint8_t* out_validity_bits,
+                                 void* workspace, int64_t workspace_bytes) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 0 || n > 0xFFFFFFFFLL)
+    FAIL(GPUQ_ERR_INVALID, "window_shift: nrows %lld out of range", (long long)n);
+  if (val.dtype != GPUQ_INT64 && val.dtype != GPUQ_FLOAT64)
+    FAIL(GPUQ_ERR_INVALID, "window_shift: unsupported dtype %d", val.dtype);
+  win_ws w; int64_t need;
+  win_ws_layout(n, &w, (char*)workspace, &need);
+  if (workspace_bytes < need)
+    FAIL(GPUQ_ERR_INVALID, "window_shift: workspace %lld < %lld",
+         (long long)workspace_bytes, (long long)need);
+  if (n == 0) return GPUQ_OK;
+  if (!val.data) FAIL(GPUQ_ERR_INVALID, "window_shift: needs a value column");
+  if (!out_validity_bits) FAIL(GPUQ_ERR_INVALID, "window_shift: needs an output bitmap");
+  /* an offset past either end of the input is past every partition */
+  if (offset > n) offset = n;
+  if (offset < -n) offset = -n;
+  wu64 dflt;
+  if (val.dtype == GPUQ_FLOAT64) memcpy(&dflt, &lit_f64, 8);
+  else memcpy(&dflt, &lit_i64, 8);
+  const int64_t nt = (n + WIN_TILE - 1) / WIN_TILE;
+  /* the peer bitmap is not needed: the partition bitmap stands in for it */
+  win_reduce_carry<WK_NONE>(s, n, WS_ONE, val, part_start, part_start, w);
+  { hipEvent_t _pe = prof_begin(s);
+  k_win_shift<<<dim3((uint32_t)nt), WIN_BLOCK, 0, s>>>(
+      n, (const wu64*)val.data, val.validity, offset, has_default != 0, dflt,
+      (const wu64*)part_start, w.prev_part, w.next_part, (wu64*)out,
+      out_validity_bits, (n + 7) / 8);
+  prof_end("win_shift", s, _pe); }
+  HIP_TRY(hipGetLastError());
+  return GPUQ_OK;
+}

@@ -81,6 +81,12 @@ class SparkPlan:
     def required_child_distribution(self) -> List[Distribution]:
         return [Distribution("unspecified") for _ in self.children]
 
+    def required_child_ordering(self) -> list:
+        """requiredChildOrdering (SparkPlan.scala): the SortOrders this node
+        needs its child's rows in; EnsureRequirements puts a SortExec below
+        a node whose child does not already deliver them."""
+        return []
+
     @property
     def output_ordering(self) -> list:
         """outputOrdering (SparkPlan.scala:180 contract): the SortOrders
@@ -358,6 +364,97 @@ class ProjectExec(_CpuNode):
     @property
     def output(self):
         return [p if isinstance(p, str) else p[0] for p in self.projections]
+
+
+WINDOW_RANK_FNS = ("row_number", "rank", "dense_rank")
+WINDOW_AGG_FNS = ("count", "sum", "min", "max", "avg")
+WINDOW_SHIFT_FNS = ("lag", "lead")
+WINDOW_FRAMES = ("rows", "range", "partition")
+
+
+@dataclass
+class WindowExpr:
+    """One window expression of a WindowExec (WindowExec.scala
+    windowExpression). fn: row_number / rank / dense_rank / count / sum / min
+    / max / avg / lag / lead. col: the argument column, None for the rank
+    functions and COUNT(*). frame, for the aggregates: "rows" (ROWS BETWEEN
+    UNBOUNDED PRECEDING AND CURRENT ROW), "range" (RANGE ... CURRENT ROW:
+    peers share a value) or "partition" (the whole partition); None is
+    Spark's default, "range" with an ORDER BY and "partition" without one.
+    offset / default are lag's and lead's (ignoreNulls = false)."""
+    fn: str
+    col: Optional[str]
+    name: str
+    frame: Optional[str] = None
+    offset: int = 1
+    default: object = None
+
+
+def _window_check(window_exprs, partition_spec, order_spec, child):
+    """the constructor checks shared by WindowExec and GpuWindowExec;
+    returns (window_exprs, partition_spec, order_spec) as lists."""
+    window_exprs = list(window_exprs)
+    partition_spec = ([partition_spec] if isinstance(partition_spec, str)
+                      else list(partition_spec))
+    order_spec = ([order_spec] if isinstance(order_spec, SortOrder)
+                  else list(order_spec))
+    names = list(child.output)
+    for e in window_exprs:
+        if e.fn not in WINDOW_RANK_FNS + WINDOW_AGG_FNS + WINDOW_SHIFT_FNS:
+            raise ValueError(f"window: unknown function {e.fn!r}")
+        if e.frame is not None and e.frame not in WINDOW_FRAMES:
+            raise ValueError(f"window: unknown frame {e.frame!r}")
+        if e.fn in WINDOW_RANK_FNS and e.col is not None:
+            raise ValueError(f"window: {e.fn} takes no column")
+        if e.fn not in WINDOW_RANK_FNS and e.fn != "count" and e.col is None:
+            raise ValueError(f"window: {e.fn} needs a column")
+        if e.fn in WINDOW_RANK_FNS + WINDOW_SHIFT_FNS and not order_spec:
+            raise ValueError(f"window: {e.fn} needs an ORDER BY")
+        if e.name in names:
+            raise ValueError(f"window: output column {e.name!r} already exists")
+        names.append(e.name)
+    return window_exprs, partition_spec, order_spec
+
+
+class _WindowSpec:
+    """what WindowExec and GpuWindowExec share: output = child's output plus
+    one column per expression, the child's ordering kept, rows clustered on
+    the partition keys and sorted by (partition keys ascending, order spec)
+    (WindowExec.scala requiredChildDistribution / requiredChildOrdering)."""
+
+    @property
+    def output(self):
+        return list(self.children[0].output) + [e.name for e in self.window_exprs]
+
+    @property
+    def output_ordering(self):
+        return self.children[0].output_ordering
+
+    def required_child_distribution(self):
+        return [Distribution("clustered", tuple(self.partition_spec))]
+
+    def required_child_ordering(self):
+        return [SortOrder(k) for k in self.partition_spec] + list(self.order_spec)
+
+    def frame_of(self, e: "WindowExpr") -> str:
+        """the frame an aggregate runs under: Spark's default when none is
+        given, and "range" without an ORDER BY is the whole partition (every
+        row is a peer of every other)."""
+        frame = e.frame or ("range" if self.order_spec else "partition")
+        if frame == "range" and not self.order_spec:
+            frame = "partition"
+        return frame
+
+
+class WindowExec(_WindowSpec, _CpuNode):
+    """window_exprs: WindowExprs; partition_spec: column names (PARTITION
+    BY); order_spec: SortOrders (ORDER BY) (execution/window/
+    WindowExec.scala)."""
+
+    def __init__(self, window_exprs, partition_spec, order_spec, child):
+        super().__init__(child)
+        self.window_exprs, self.partition_spec, self.order_spec = \
+            _window_check(window_exprs, partition_spec, order_spec, child)
 
 
 class RangeExec(_CpuNode):
@@ -1578,6 +1675,78 @@ class GpuProjectExec(SparkPlan):
             yield ColumnarBatch(cols, validity=validity or None)
 
 
+class GpuWindowExec(_WindowSpec, SparkPlan):
+    """Replaces WindowExec (execution/window/WindowExec.scala). As in Spark
+    the rows arrive clustered on the partition keys and sorted by (partition
+    keys, order keys) — the SortExec EnsureRequirements put below this node;
+    nothing is sorted here. A whole-partition operator: the child's batches
+    are concatenated, the partition / peer-group bitmaps are computed once
+    and every expression is one segmented scan (gpuq_window_scan) or shift
+    (gpuq_window_shift) under them. Yields one batch: every input column and
+    bitmap untouched, plus one column per expression. avg (float64 only) is
+    windowed SUM / cast(windowed COUNT), NULL where the count is 0."""
+
+    def __init__(self, window_exprs, partition_spec, order_spec, child):
+        super().__init__(child)
+        self.window_exprs, self.partition_spec, self.order_spec = \
+            _window_check(window_exprs, partition_spec, order_spec, child)
+
+    @property
+    def supports_columnar(self):
+        return True
+
+    def _eval(self, gpuq, e, batch, n, part_bits, peer_bits, ws):
+        """(column, validity or None) of one expression."""
+        if e.fn in WINDOW_RANK_FNS:
+            return gpuq.window_scan(e.fn, "rows", part_bits, peer_bits, n=n,
+                                    workspace=ws)
+        val = batch.column(e.col) if e.col is not None else None
+        valid = batch.validity(e.col) if e.col is not None else None
+        if e.fn in WINDOW_SHIFT_FNS:
+            off = -e.offset if e.fn == "lag" else e.offset
+            return gpuq.window_shift(val, off, part_bits, validity=valid,
+                                     default=e.default, workspace=ws)
+        frame = self.frame_of(e)
+        if e.fn != "avg":
+            return gpuq.window_scan(e.fn, frame, part_bits, peer_bits, val=val,
+                                    validity=valid, n=n, workspace=ws)
+        if val.dtype != torch.float64:
+            raise ValueError(f"window: avg({e.col}) over {val.dtype} "
+                             "unsupported (float64 columns only)")
+        total, tvalid = gpuq.window_scan("sum", frame, part_bits, peer_bits,
+                                         val=val, validity=valid, workspace=ws)
+        cnt, _ = gpuq.window_scan("count", frame, part_bits, peer_bits,
+                                  val=val, validity=valid, workspace=ws)
+        # x / 0 is NULL: the rows whose frame holds no non-NULL value
+        return gpuq.project_binop_nullable(total, "/", b=gpuq.cast_i64_f64(cnt),
+                                           a_validity=tvalid)
+
+    def execute_columnar(self):
+        import torch.distributed as dist
+        from . import gpuq
+        assert (self.partition_spec or not dist.is_initialized()
+                or dist.get_world_size() == 1), \
+            "multi-rank window without PARTITION BY unsupported"
+        batches = list(self.children[0].execute_columnar())
+        assert batches, "window over a batchless child"
+        batch = concat_batches(batches)
+        n = batch.num_rows()
+        keys = list(self.partition_spec) + [o.key for o in self.order_spec]
+        part_bits, peer_bits = gpuq.window_boundaries(
+            [batch.column(k) for k in keys],
+            [batch.validity(k) for k in keys], len(self.partition_spec), n=n)
+        ws = gpuq.window_workspace(n)
+        cols = batch.columns()
+        validity = {k: batch.validity(k) for k in cols
+                    if batch.validity(k) is not None}
+        for e in self.window_exprs:
+            cols[e.name], v = self._eval(gpuq, e, batch, n, part_bits,
+                                         peer_bits, ws)
+            if v is not None:
+                validity[e.name] = v
+        yield ColumnarBatch(cols, validity=validity or None)
+
+
 class GpuBroadcastExchangeExec(SparkPlan):
     """Replaces BroadcastExchangeExec: RCCL all-gather of the build-side
     batch across ranks (single-rank: identity). Unlike the shuffled
@@ -1684,6 +1853,9 @@ class GpuColumnarRule:
             return GpuFilterExec(plan.col, plan.op, plan.literal, *children)
         if isinstance(plan, ProjectExec):
             return GpuProjectExec(plan.projections, *children)
+        if isinstance(plan, WindowExec):
+            return GpuWindowExec(plan.window_exprs, plan.partition_spec,
+                                 plan.order_spec, *children)
         if isinstance(plan, RangeExec):
             return GpuRangeExec(plan.n, plan.start, plan.step, plan.name)
         if isinstance(plan, ParquetScanExec):

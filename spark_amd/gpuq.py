@@ -191,6 +191,18 @@ def lib() -> ctypes.CDLL:
         L.gpuq_range_i64.argtypes = [vp, i64, i64, i64, vp]
         L.gpuq_cast_i64_f64.restype = i32
         L.gpuq_cast_i64_f64.argtypes = [vp, i64, vp, vp]
+        L.gpuq_window_boundaries.restype = i32
+        L.gpuq_window_boundaries.argtypes = [vp, i64, ctypes.POINTER(_Col), i32,
+                                             i32, vp, vp]
+        L.gpuq_window_workspace_bytes.restype = i64
+        L.gpuq_window_workspace_bytes.argtypes = [i64]
+        L.gpuq_window_scan.restype = i32
+        L.gpuq_window_scan.argtypes = [vp, i64, i32, i32, _Col, vp, vp, vp, vp,
+                                       vp, i64]
+        L.gpuq_window_shift.restype = i32
+        L.gpuq_window_shift.argtypes = [vp, i64, _Col, i64, i32,
+                                        ctypes.c_double, i64, vp, vp, vp,
+                                        vp, i64]
         L.gpuq_profiling.restype = None
         L.gpuq_profiling.argtypes = [i32]
         L.gpuq_kernel_stats_reset.restype = None
@@ -989,3 +1001,154 @@ def hash_agg_partitioned(keys: torch.Tensor, vals: torch.Tensor, capacity: int,
         ocnt.data_ptr(), ctypes.byref(ng)))
     gn = ng.value
     return ok[:gn], okv[:gn], osum[:gn], osv[:gn], ocnt[:gn]
+
+
+# ---------------- window functions (segmented scans) ----------------
+# mirrors of the #defines in csrc/gpuq.hip: rows per block of the window
+# kernels, and the number of tile summaries one step of the carry kernel
+# covers
+WIN_TILE = 2048
+WIN_CARRY_SPAN = 2048
+
+WIN_OP = {"row_number": 0, "rank": 1, "dense_rank": 2, "count": 3, "sum": 4,
+          "min": 5, "max": 6}
+WIN_FRAME = {"rows": 0, "range": 1, "partition": 2}
+
+
+def _bitmap_words(n: int) -> int:
+    return (n + 63) // 64
+
+
+def window_boundaries(keys, validities, npart: int, n: int = None):
+    """Partition-start and peer-group-start bitmaps of a batch sorted by
+    (partition keys, order keys): keys[:npart] are the partition columns,
+    keys[npart:] the order columns (int64 / float64), validities a list of
+    the same length (entries may be None) or None. Returns (part_bits,
+    peer_bits), int64 tensors of ceil(n / 64) words, LSB-first. n is taken
+    from the keys; it must be given when there are none (one partition of
+    one peer group)."""
+    keys = list(keys)
+    nkeys = len(keys)
+    validities = list(validities) if validities is not None else [None] * nkeys
+    if len(validities) != nkeys:
+        raise ValueError(f"window_boundaries: {nkeys} keys but "
+                         f"{len(validities)} validity entries")
+    if not 0 <= npart <= nkeys:
+        raise ValueError(f"window_boundaries: npart {npart} outside 0..{nkeys}")
+    if nkeys == 0:
+        if n is None:
+            raise ValueError("window_boundaries: n is needed without keys")
+        dev = "cuda"
+    else:
+        if n is None:
+            n = keys[0].numel()
+        dev = keys[0].device
+    for k in keys:
+        if k.dtype not in (torch.int64, torch.float64):
+            raise ValueError(f"window_boundaries: unsupported dtype {k.dtype}")
+        if k.numel() != n:
+            raise ValueError(f"window_boundaries: key has {k.numel()} rows, "
+                             f"expected {n}")
+    part = torch.empty(_bitmap_words(n), dtype=torch.int64, device=dev)
+    peer = torch.empty(_bitmap_words(n), dtype=torch.int64, device=dev)
+    arr = (_Col * max(nkeys, 1))(*[_col(k, v) for k, v in zip(keys, validities)])
+    _check(lib().gpuq_window_boundaries(_stream(), n, arr, nkeys, npart,
+                                        part.data_ptr(), peer.data_ptr()))
+    return part, peer
+
+
+def window_workspace(n: int, device="cuda") -> torch.Tensor:
+    return torch.empty(lib().gpuq_window_workspace_bytes(n), dtype=torch.uint8,
+                       device=device)
+
+
+def _check_bitmaps(who: str, n: int, *bitmaps):
+    for b in bitmaps:
+        if b.dtype != torch.int64 or b.numel() != _bitmap_words(n):
+            raise ValueError(f"{who}: a boundary bitmap must be "
+                             f"{_bitmap_words(n)} int64 words for {n} rows")
+
+
+def window_scan(op: str, frame: str, part_bits, peer_bits, val=None,
+                validity=None, n: int = None, workspace=None):
+    """One window expression over the bitmaps of window_boundaries. op:
+    row_number / rank / dense_rank (frame "rows", no val), count (val=None
+    is COUNT(*)), sum / min / max; frame: "rows" | "range" | "partition"
+    (every frame starts at UNBOUNDED PRECEDING). Returns (out,
+    out_validity_or_None): the bitmap only for sum / min / max over a column
+    that has one. n is taken from val and must be given without it."""
+    if op not in WIN_OP:
+        raise ValueError(f"window_scan: bad op {op!r}")
+    if frame not in WIN_FRAME:
+        raise ValueError(f"window_scan: bad frame {frame!r}")
+    rank_op = WIN_OP[op] <= 2
+    if rank_op and (val is not None or frame != "rows"):
+        raise ValueError(f"window_scan: {op} takes no column and the rows frame")
+    if val is None:
+        if validity is not None:
+            raise ValueError("window_scan: validity without a column")
+        if op in ("sum", "min", "max"):
+            raise ValueError(f"window_scan: {op} needs a column")
+        if n is None:
+            raise ValueError("window_scan: n is needed without a column")
+    else:
+        if val.dtype not in (torch.int64, torch.float64):
+            raise ValueError(f"window_scan: unsupported dtype {val.dtype}")
+        if n is not None and n != val.numel():
+            raise ValueError("window_scan: n differs from the column length")
+        n = val.numel()
+    _check_bitmaps("window_scan", n, part_bits, peer_bits)
+    dev = part_bits.device
+    if workspace is None:
+        workspace = window_workspace(n, dev)
+    out_dtype = torch.float64 if (val is not None and val.dtype == torch.float64
+                                  and op in ("sum", "min", "max")) else torch.int64
+    out = torch.empty(n, dtype=out_dtype, device=dev)
+    bits = None
+    if validity is not None and op in ("sum", "min", "max"):
+        bits = torch.empty(_bitmap_bytes(n), dtype=torch.uint8, device=dev)
+    col = _col(val, validity) if val is not None else _Col(None, None, GPUQ_INT64)
+    _check(lib().gpuq_window_scan(_stream(), n, WIN_OP[op], WIN_FRAME[frame], col,
+                                  part_bits.data_ptr(), peer_bits.data_ptr(),
+                                  out.data_ptr(), _dp(bits),
+                                  workspace.data_ptr(), workspace.numel()))
+    return out, bits
+
+
+def window_shift(val, offset: int, part_bits, validity=None, default=None,
+                 workspace=None):
+    """lag (offset < 0) / lead (offset > 0) inside the partitions of
+    part_bits: out[i] = val[i + offset] with its own NULL-ness, or `default`
+    (NULL when None) where that row is outside i's partition. Returns (out,
+    out_validity). An int64 column takes only an integral default."""
+    if val.dtype not in (torch.int64, torch.float64):
+        raise ValueError(f"window_shift: unsupported dtype {val.dtype}")
+    n = val.numel()
+    _check_bitmaps("window_shift", n, part_bits)
+    lit_f, lit_i = 0.0, 0
+    if default is not None:
+        if val.dtype == torch.float64:
+            lit_f = float(default)
+        else:
+            import math
+            if isinstance(default, float) and (not math.isfinite(default)
+                                               or default != int(default)):
+                raise ValueError(f"window_shift: non-integral default "
+                                 f"{default!r} on an int64 column")
+            lit_i = int(default)
+            if not -(1 << 63) <= lit_i < (1 << 63):
+                raise ValueError(f"window_shift: default {default!r} exceeds int64")
+    offset = int(offset)
+    if not -(1 << 63) <= offset < (1 << 63):
+        raise ValueError("window_shift: offset exceeds int64")
+    dev = val.device
+    if workspace is None:
+        workspace = window_workspace(n, dev)
+    out = torch.empty(n, dtype=val.dtype, device=dev)
+    bits = torch.empty(_bitmap_bytes(n), dtype=torch.uint8, device=dev)
+    _check(lib().gpuq_window_shift(_stream(), n, _col(val, validity), offset,
+                                   int(default is not None), lit_f, lit_i,
+                                   part_bits.data_ptr(), out.data_ptr(),
+                                   bits.data_ptr(), workspace.data_ptr(),
+                                   workspace.numel()))
+    return out, bits
