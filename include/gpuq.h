@@ -452,7 +452,8 @@ int gpuq_join_keys_unmatched_build(void* stream, void* workspace, int64_t capaci
 /* compound predicate (gpuq_filter_expr); WHERE keeps only TRUE      */
 /* (a NULL result drops the row). Stable compaction: the             */
 /* first *out_count entries of out_perm are the passing rows in      */
-/* input order. Project: elementwise a OP b (column or literal).     */
+/* input order. Project: elementwise a OP b (column or literal), or  */
+/* a list of compound expressions in one pass (gpuq_project_expr).   */
 /* ---------------------------------------------------------------- */
 
 /* Comparison rules (Spark, non-ANSI):
@@ -570,6 +571,112 @@ int gpuq_project_binop_nullable(void* stream, int64_t nrows, gpuq_col a,
                                 gpuq_col b, double lit_f64, int64_t lit_i64,
                                 int32_t op, void* out,
                                 uint8_t* out_validity_bits);
+
+/* Compound SELECT-list expressions in one fused pass: a typed postfix program
+ * over up to GPUQ_EXPR_MAX_COLS columns, evaluated once per row on a stack of
+ * at most GPUQ_EXPR_MAX_DEPTH slots, producing up to GPUQ_EXPR_MAX_OUTS output
+ * columns from ONE read of each referenced input column. The host layer
+ * (spark_amd/expression.py) lowers arithmetic trees, casts, comparisons used
+ * as values, If / CaseWhen and Coalesce to it.
+ *
+ * Every instruction states its operand type in `dtype`; the host decides all
+ * typing and the entry point checks it with a stack simulation, so the kernel
+ * tracks no types at run time. Stack types are GPUQ_INT64, GPUQ_FLOAT64 and
+ * the stack-only GPUQ_EXPR_BOOL. A slot is a 64-bit payload plus a NULL flag;
+ * BOOL is payload 0 / 1; the payload of a NULL slot is unspecified.
+ *
+ * Semantics (Spark, non-ANSI):
+ *  COL     push cols[arg]; NULL where its bitmap says so. dtype = its dtype.
+ *  LIT     push the literal of type dtype (lit_f64 for float64, lit_i64 for
+ *          int64 and for BOOL, which takes 0 / 1). arg == 1: the typed NULL
+ *          literal; arg must be 0 or 1.
+ *  REF     push the value and NULL-ness OUT arg already produced for the row.
+ *  ARITH   arg = GPUQ_BINOP_ADD / SUB / MUL / DIV. Pops b (top), then a, and
+ *          pushes a OP b by the arithmetic rules of
+ *          gpuq_project_binop_nullable: int64 + - * wrap, / truncates toward
+ *          zero, INT64_MIN / -1 == INT64_MIN; float64 is the IEEE result of
+ *          that single operation (nothing is contracted across instructions).
+ *          NULL if an operand is NULL or the op is / and the divisor is zero
+ *          (float64: 0.0 and -0.0).
+ *  NEG ABS int64 wraps: -INT64_MIN == abs(INT64_MIN) == INT64_MIN. float64
+ *          flips / clears the sign bit (NaN included). NULL stays NULL.
+ *  CAST    dtype = source type, arg = target type: int64 -> float64 (round to
+ *          nearest even), float64 -> int64 (Java's (long) d: truncates toward
+ *          zero, NaN -> 0, values at or beyond +/-2^63 saturate to INT64_MAX /
+ *          INT64_MIN), BOOL -> int64 (0 / 1). NULL stays NULL.
+ *  CMP     arg = GPUQ_CMP_*. Pops b then a of equal int64 / float64 type and
+ *          pushes BOOL by exactly the comparison rules above (total order on
+ *          float64, -0.0 == 0.0, NaN == NaN and greatest). NULL if an operand
+ *          is NULL.
+ *  IS_NULL / IS_NOT_NULL  pop one value of any type (dtype = its type), push
+ *          a BOOL that is never NULL.
+ *  AND OR NOT  Kleene logic on BOOL, the truth tables of gpuq_filter_expr.
+ *  SELECT  pops cond (top, BOOL), then `then`, then `else` (equal types,
+ *          dtype = that type). Pushes `then` iff cond is TRUE, otherwise
+ *          `else` — a NULL cond picks `else`, as Spark's If / CaseWhen do —
+ *          with the chosen branch's NULL-ness. Both branches are evaluated;
+ *          a division by zero in the branch not taken is a discarded NULL.
+ *  COALESCE  pops b (top), then a, of equal types: a if a is non-NULL, else b.
+ *  OUT     pops the top (int64 / float64, == out_dtypes[arg] == dtype), writes
+ *          it to outs[arg] (0 where the row is NULL) and, when
+ *          out_validity_bits[arg] is non-NULL, the row's validity bit. */
+#define GPUQ_EXPR_BOOL 3   /* stack-only type; not a column dtype */
+
+#define GPUQ_EXPR_COL 0
+#define GPUQ_EXPR_LIT 1
+#define GPUQ_EXPR_REF 2
+#define GPUQ_EXPR_ARITH 3
+#define GPUQ_EXPR_NEG 4
+#define GPUQ_EXPR_ABS 5
+#define GPUQ_EXPR_CAST 6
+#define GPUQ_EXPR_CMP 7
+#define GPUQ_EXPR_IS_NULL 8
+#define GPUQ_EXPR_IS_NOT_NULL 9
+#define GPUQ_EXPR_AND 10
+#define GPUQ_EXPR_OR 11
+#define GPUQ_EXPR_NOT 12
+#define GPUQ_EXPR_SELECT 13
+#define GPUQ_EXPR_COALESCE 14
+#define GPUQ_EXPR_OUT 15
+
+#define GPUQ_EXPR_MAX_INSNS 48
+#define GPUQ_EXPR_MAX_COLS 8
+#define GPUQ_EXPR_MAX_OUTS 4
+#define GPUQ_EXPR_MAX_DEPTH 8
+
+typedef struct gpuq_expr_insn {
+  int32_t opcode;   /* GPUQ_EXPR_* */
+  int32_t arg;      /* column / output index, binop, comparison, cast target, NULL-literal flag */
+  int32_t dtype;    /* operand type: GPUQ_INT64 / GPUQ_FLOAT64 / GPUQ_EXPR_BOOL */
+  int32_t pad;      /* ignored */
+  int64_t lit_i64;
+  double lit_f64;
+} gpuq_expr_insn;
+
+/* Needs no workspace and never synchronises with the host. prog is a HOST
+ * array, copied into the kernel arguments. outs[k] is nrows 8-byte values of
+ * out_dtypes[k]; out_validity_bits[k] is (nrows + 7) / 8 bytes (spare bits of
+ * the last byte come out zero, nothing past it is written, no alignment is
+ * required) or NULL, by which the caller asserts that output k cannot be NULL:
+ * nothing is recorded for it then. Every referenced column (and bitmap) is
+ * read once and never written. Outputs and their bitmaps must not overlap an
+ * input or each other. nrows == 0 returns GPUQ_OK with nothing launched.
+ * Returned as GPUQ_ERR_INVALID before any HIP call: nrows < 0 or
+ * > 0xFFFFFFFF; ncols outside 0..GPUQ_EXPR_MAX_COLS, ninsns outside
+ * 1..GPUQ_EXPR_MAX_INSNS, nouts outside 1..GPUQ_EXPR_MAX_OUTS; a column or
+ * output dtype other than int64 / float64; a bad opcode, binop (RSUB
+ * included), comparison, cast pair or NULL-literal flag; a column, output or
+ * REF index out of range; a REF to an output not yet written; an output
+ * written twice or never; a declared dtype that differs from the type the
+ * stack simulation infers; operand types that differ; BOOL given to ARITH,
+ * NEG, ABS, CMP or OUT; non-BOOL given to AND, OR, NOT or as a SELECT
+ * condition; stack underflow; depth over GPUQ_EXPR_MAX_DEPTH; a program that
+ * does not end at depth 0; a NULL outs[k] with nrows > 0. */
+int gpuq_project_expr(void* stream, int64_t nrows,
+                      const gpuq_col* cols, int32_t ncols,
+                      const gpuq_expr_insn* prog /* HOST */, int32_t ninsns,
+                      void* const* outs, uint8_t* const* out_validity_bits,
+                      const int32_t* out_dtypes, int32_t nouts);
 
 /* int64 -> float64 cast (AVG evaluation: sum / cast(count)) */
 int gpuq_cast_i64_f64(void* stream, int64_t nrows, const int64_t* in, double* out);

@@ -5673,6 +5673,517 @@ extern "C" int gpuq_project_binop_nullable(void* stream, int64_t n, gpuq_col a,
   return GPUQ_OK;
 }
 
+/* ---- compound expressions: one fused pass (gpuq_project_expr) ----
+ *
+ * k_expr_eval has k_pred_mask's shape: one block per EXPR_TILE rows, row r of
+ * thread t is tile + r * EXPR_BLOCK + t, instructions outer and the rows
+ * inner and unrolled (a COL issues its loads back to back), the program and
+ * the column / output tables by value in the kernel arguments. The program
+ * counter, the opcode, the dtype and the stack depth are the same in every
+ * lane, so every branch of the interpreter is wave-uniform.
+ *
+ * The value stack lives in registers as a shifting stack of named slots:
+ * slot 0 is the top, a push moves every slot one down, a pop one up, and every
+ * operand sits at a fixed slot (a binary op reads slots 1 and 0), so nothing
+ * is indexed by a runtime value. The host's stack simulation knows the depth
+ * in front of every instruction and leaves it in the instruction's pad word;
+ * while the depth stays within EXPR_SHALLOW only that many slots move (a
+ * wave-uniform branch), which is what Q1-sized programs pay. NULL flags are
+ * bit d of one word per row and shift with the slots. The compiler
+ * structurizes this loop
+ * although its branches are uniform, and the joins keep two copies of the
+ * stack alive, so registers go with the slot count: hence the 4-slot kernel
+ * beside the 8-slot one, and 4 rows per thread (compile table in DESIGN.md).
+ *
+ * OUT stores the value (0 under a NULL), ballots the valid flags — a wave
+ * covers 64 consecutive rows from a multiple of 64, i.e. 8 whole bitmap bytes,
+ * every 8th lane stores its byte, no atomics; tiles are multiples of 64 rows
+ * so no two blocks share a byte — and keeps the row's NULL flag for REF. REF
+ * re-reads the value its own thread stored.
+ */
+#define EXPR_BLOCK 256
+#define EXPR_ITEMS 4
+#define EXPR_TILE (EXPR_BLOCK * EXPR_ITEMS)   /* 1024 rows per block */
+#define EXPR_SHALLOW 4    /* slots of the small kernel and of the cheap shifts */
+
+struct expr_args {
+  const void* data[GPUQ_EXPR_MAX_COLS];
+  const uint8_t* validity[GPUQ_EXPR_MAX_COLS];
+  void* out[GPUQ_EXPR_MAX_OUTS];
+  uint8_t* out_bits[GPUQ_EXPR_MAX_OUTS];
+  int32_t ninsns;
+  gpuq_expr_insn insn[GPUQ_EXPR_MAX_INSNS];   /* pad = stack depth in front */
+};
+
+template <int DEPTH>
+struct expr_regs {
+  uint64_t v[DEPTH][EXPR_ITEMS];
+  uint32_t nl[EXPR_ITEMS];      /* bit d: slot d is NULL */
+  uint32_t onull[EXPR_ITEMS];   /* bit k: OUT k wrote a NULL */
+};
+
+DEV double expr_f(uint64_t x) { return __longlong_as_double((long long)x); }
+DEV uint64_t expr_u(double x) { return (uint64_t)__double_as_longlong(x); }
+
+/* Java's (long) d, without a branch: NaN becomes 0, the value is clamped to
+ * [-2^63, 2^63 - 1024] (the largest double below 2^63) so the conversion is
+ * defined, and what was at or beyond 2^63 then reads INT64_MAX; -2^63 and
+ * below convert to INT64_MIN by the clamp itself. */
+DEV int64_t expr_f64_to_i64(double d) {
+  double c = d != d ? 0.0 : d;
+  c = fmax(fmin(c, 9223372036854774784.0), -9223372036854775808.0);
+  int64_t t = (int64_t)c;
+  return d >= 9223372036854775808.0 ? INT64_MAX : t;
+}
+
+/* filter_cmp_f64's truth table (total order, -0.0 == 0.0, NaN == NaN and
+ * greatest) without its divergent branch on NaN: op is wave-uniform here, so
+ * this leaves no lane-dependent control flow in the interpreter loop. */
+DEV bool expr_cmp_f64(double x, int op, double y) {
+  const bool xn = x != x, yn = y != y;
+  const bool eq = (xn & yn) | (x == y);
+  const bool lt = !xn & (yn | (x < y));
+  switch (op) {
+    case GPUQ_CMP_EQ: return eq;
+    case GPUQ_CMP_LT: return lt;
+    case GPUQ_CMP_LE: return lt | eq;
+    case GPUQ_CMP_GT: return !(lt | eq);
+    case GPUQ_CMP_GE: return !lt;
+    default: return !eq;
+  }
+}
+
+#define EXPR_ROWS _Pragma("unroll") for (int r = 0; r < EXPR_ITEMS; r++)
+#define EXPR_NL(d) ((s.nl[r] >> (d)) & 1u)
+#define EXPR_SET_NL(d, x) s.nl[r] = (s.nl[r] & ~(1u << (d))) | ((uint32_t)(x) << (d))
+
+/* make room on top: slot d-1 moves to slot d for d = LAST .. 1 */
+template <int LAST, typename REGS>
+DEV void expr_shift_down(REGS& s) {
+  #pragma unroll
+  for (int d = LAST; d >= 1; d--) { EXPR_ROWS s.v[d][r] = s.v[d - 1][r]; }
+  EXPR_ROWS s.nl[r] <<= 1;
+}
+
+/* drop the BY top slots: slot d+BY moves to slot d for d = 0 .. LAST */
+template <int BY, int LAST, typename REGS>
+DEV void expr_drop(REGS& s) {
+  #pragma unroll
+  for (int d = 0; d <= LAST; d++) { EXPR_ROWS s.v[d][r] = s.v[d + BY][r]; }
+  EXPR_ROWS s.nl[r] >>= BY;
+}
+
+/* a OP b on slots 1 and 0 into slot 1, the operator and type fixed at compile
+ * time so the row loop holds no dispatch */
+template <int OP, bool F64, typename REGS>
+DEV void expr_arith(REGS& s) {
+  EXPR_ROWS {
+    const uint64_t x = s.v[1][r], y = s.v[0][r];
+    s.v[1][r] = F64 ? expr_u(binop_f64<OP>(expr_f(x), expr_f(y)))
+                    : (uint64_t)binop_i64<OP>((int64_t)x, (int64_t)y);
+    EXPR_SET_NL(1, EXPR_NL(1) | EXPR_NL(0));
+  }
+}
+
+template <int OP, bool F64, typename REGS>
+DEV void expr_cmp(REGS& s) {
+  EXPR_ROWS {
+    const bool t = F64
+        ? expr_cmp_f64(expr_f(s.v[1][r]), OP, expr_f(s.v[0][r]))
+        : filter_cmp_i64((int64_t)s.v[1][r], OP, (int64_t)s.v[0][r]);
+    s.v[1][r] = t ? 1 : 0;
+    EXPR_SET_NL(1, EXPR_NL(1) | EXPR_NL(0));
+  }
+}
+
+#define EXPR_BY_TYPE(FN, OP) do { \
+    if (f64) FN<OP, true>(s); else FN<OP, false>(s); } while (0)
+
+/* One instruction with `depth` values on the stack in front of it. FULL: every
+ * row of the block's tile is below n, so no load or store is predicated (no
+ * exec-mask branch around them; only the int64 divide keeps lane-dependent
+ * branches of its own). In a full tile all eight lanes of a bitmap byte store
+ * it, with the same value. */
+template <bool FULL, int DEPTH>
+DEV void expr_step(expr_regs<DEPTH>& s, const expr_args& a, const int pc,
+                   const int64_t n, const int64_t base, const int lane) {
+  const int depth = a.insn[pc].pad;
+  const int opcode = a.insn[pc].opcode;
+  const int arg = a.insn[pc].arg;
+  const bool f64 = a.insn[pc].dtype == GPUQ_FLOAT64;
+  if (opcode <= GPUQ_EXPR_REF) {
+    {
+      constexpr int D = 0;   /* the new top */
+      if (DEPTH == EXPR_SHALLOW || depth < EXPR_SHALLOW) expr_shift_down<EXPR_SHALLOW - 1>(s);
+      else expr_shift_down<DEPTH - 1>(s);
+      if (opcode == GPUQ_EXPR_COL) {
+        const uint64_t* d = (const uint64_t*)a.data[arg];
+        const uint8_t* v = a.validity[arg];
+        EXPR_ROWS {
+          int64_t i = base + r * EXPR_BLOCK;
+          bool in = FULL || i < n;
+          s.v[D][r] = in ? d[i] : 0;
+          EXPR_SET_NL(D, !(in && bit_valid(v, i)));
+        }
+      } else if (opcode == GPUQ_EXPR_LIT) {
+        const uint64_t lit = f64 ? expr_u(a.insn[pc].lit_f64)
+                                 : (uint64_t)a.insn[pc].lit_i64;
+        const uint32_t isnull = arg != 0;
+        EXPR_ROWS { s.v[D][r] = lit; EXPR_SET_NL(D, isnull); }
+      } else {   /* REF: what this thread stored for OUT arg */
+        const uint64_t* o = (const uint64_t*)a.out[arg];
+        EXPR_ROWS {
+          int64_t i = base + r * EXPR_BLOCK;
+          s.v[D][r] = FULL || i < n ? o[i] : 0;
+          EXPR_SET_NL(D, (s.onull[r] >> arg) & 1u);
+        }
+      }
+    }
+  } else if (opcode == GPUQ_EXPR_ARITH || opcode == GPUQ_EXPR_CMP ||
+             opcode == GPUQ_EXPR_AND || opcode == GPUQ_EXPR_OR ||
+             opcode == GPUQ_EXPR_COALESCE) {
+    {
+      constexpr int A = 1, B = 0;   /* the result replaces a, then b is dropped */
+      if (opcode == GPUQ_EXPR_ARITH && arg == GPUQ_BINOP_DIV) {
+        /* the divide expansions are long: one row at a time (the barrier
+         * keeps the scheduler from interleaving the rows), or their
+         * temporaries set the kernel's register count */
+        if (f64) {
+          EXPR_ROWS {
+            const double fy = expr_f(s.v[B][r]);
+            s.v[A][r] = expr_u(binop_f64<3>(expr_f(s.v[A][r]), fy));
+            EXPR_SET_NL(A, EXPR_NL(A) | EXPR_NL(B) | (uint32_t)(fy == 0.0));
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        } else {
+          EXPR_ROWS {
+            const int64_t iy = (int64_t)s.v[B][r];
+            /* a zero divisor (also under a NULL) divides by 1: no trap, and
+             * the row is NULL anyway */
+            s.v[A][r] = (uint64_t)binop_i64<3>((int64_t)s.v[A][r], iy == 0 ? 1 : iy);
+            EXPR_SET_NL(A, EXPR_NL(A) | EXPR_NL(B) | (uint32_t)(iy == 0));
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+      } else if (opcode == GPUQ_EXPR_ARITH) {
+        if (arg == GPUQ_BINOP_ADD) EXPR_BY_TYPE(expr_arith, GPUQ_BINOP_ADD);
+        else if (arg == GPUQ_BINOP_SUB) EXPR_BY_TYPE(expr_arith, GPUQ_BINOP_SUB);
+        else EXPR_BY_TYPE(expr_arith, GPUQ_BINOP_MUL);
+      } else if (opcode == GPUQ_EXPR_CMP) {
+        switch (arg) {
+          case GPUQ_CMP_EQ: EXPR_BY_TYPE(expr_cmp, GPUQ_CMP_EQ); break;
+          case GPUQ_CMP_LT: EXPR_BY_TYPE(expr_cmp, GPUQ_CMP_LT); break;
+          case GPUQ_CMP_LE: EXPR_BY_TYPE(expr_cmp, GPUQ_CMP_LE); break;
+          case GPUQ_CMP_GT: EXPR_BY_TYPE(expr_cmp, GPUQ_CMP_GT); break;
+          case GPUQ_CMP_GE: EXPR_BY_TYPE(expr_cmp, GPUQ_CMP_GE); break;
+          default: EXPR_BY_TYPE(expr_cmp, GPUQ_CMP_NE); break;
+        }
+      } else if (opcode == GPUQ_EXPR_COALESCE) {
+        EXPR_ROWS {
+          const uint32_t an = EXPR_NL(A);
+          s.v[A][r] = an ? s.v[B][r] : s.v[A][r];
+          EXPR_SET_NL(A, an & EXPR_NL(B));
+        }
+      } else {   /* AND / OR: the deciding value (FALSE / TRUE) wins over NULL */
+        const uint32_t win = opcode == GPUQ_EXPR_OR ? 1u : 0u;
+        EXPR_ROWS {
+          uint32_t an = EXPR_NL(A), bn = EXPR_NL(B);
+          uint32_t aw = !an && ((uint32_t)s.v[A][r] & 1u) == win;
+          uint32_t bw = !bn && ((uint32_t)s.v[B][r] & 1u) == win;
+          uint32_t decided = aw | bw;
+          s.v[A][r] = decided ? win : (win ^ 1u);
+          EXPR_SET_NL(A, !decided && (an | bn));
+        }
+      }
+      if (DEPTH == EXPR_SHALLOW || depth <= EXPR_SHALLOW) expr_drop<1, EXPR_SHALLOW - 2>(s);
+      else expr_drop<1, DEPTH - 2>(s);
+    }
+  } else if (opcode == GPUQ_EXPR_SELECT) {
+    constexpr int E = 2, T = 1, C = 0;
+    EXPR_ROWS {
+      const bool take = (EXPR_NL(C) == 0u) & ((s.v[C][r] & 1u) != 0u);
+      s.v[E][r] = take ? s.v[T][r] : s.v[E][r];
+      EXPR_SET_NL(E, take ? EXPR_NL(T) : EXPR_NL(E));
+    }
+    if (DEPTH == EXPR_SHALLOW || depth <= EXPR_SHALLOW) expr_drop<2, EXPR_SHALLOW - 3>(s);
+    else expr_drop<2, DEPTH - 3>(s);
+  } else {   /* one operand on top */
+    {
+      constexpr int A = 0;
+      if (opcode == GPUQ_EXPR_NEG) {
+        if (f64) { EXPR_ROWS s.v[A][r] ^= SIGNBIT; }
+        else { EXPR_ROWS s.v[A][r] = 0ULL - s.v[A][r]; }
+      } else if (opcode == GPUQ_EXPR_ABS) {
+        if (f64) { EXPR_ROWS s.v[A][r] &= ~SIGNBIT; }
+        else {
+          EXPR_ROWS {
+            const uint64_t x = s.v[A][r];
+            s.v[A][r] = (int64_t)x < 0 ? 0ULL - x : x;
+          }
+        }
+      } else if (opcode == GPUQ_EXPR_CAST) {
+        /* dtype is the source: f64 -> i64, else i64 -> f64 or BOOL -> i64 */
+        if (f64) {
+          EXPR_ROWS {
+            s.v[A][r] = (uint64_t)expr_f64_to_i64(expr_f(s.v[A][r]));
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        } else if (arg == GPUQ_FLOAT64) {
+          EXPR_ROWS s.v[A][r] = expr_u((double)(int64_t)s.v[A][r]);
+        } else {
+          EXPR_ROWS s.v[A][r] &= 1u;
+        }
+      } else if (opcode == GPUQ_EXPR_IS_NULL || opcode == GPUQ_EXPR_IS_NOT_NULL) {
+        const uint32_t flip = opcode == GPUQ_EXPR_IS_NOT_NULL ? 1u : 0u;
+        EXPR_ROWS { s.v[A][r] = EXPR_NL(A) ^ flip; EXPR_SET_NL(A, 0u); }
+      } else if (opcode == GPUQ_EXPR_NOT) {
+        EXPR_ROWS s.v[A][r] = (s.v[A][r] & 1u) ^ 1u;
+      } else {   /* OUT */
+        uint64_t* o = (uint64_t*)a.out[arg];
+        uint8_t* bits = a.out_bits[arg];
+        EXPR_ROWS {
+          int64_t i = base + r * EXPR_BLOCK;
+          bool in = FULL || i < n;
+          uint32_t nul = EXPR_NL(A);
+          if (in) o[i] = nul ? 0 : s.v[A][r];
+          s.onull[r] = (s.onull[r] & ~(1u << arg)) | (nul << arg);
+          if (bits) {   /* wave-uniform: all 64 lanes reach the ballot */
+            unsigned long long m = __ballot(in && !nul);
+            if (FULL || ((lane & 7) == 0 && in)) bits[i >> 3] = (uint8_t)(m >> (lane & ~7));
+          }
+        }
+        if (DEPTH == EXPR_SHALLOW || depth <= EXPR_SHALLOW) expr_drop<1, EXPR_SHALLOW - 2>(s);
+        else expr_drop<1, DEPTH - 2>(s);
+      }
+    }
+  }
+}
+
+template <bool FULL, int DEPTH>
+DEV void expr_run(const int64_t n, const expr_args& a) {
+  const int64_t base = (int64_t)blockIdx.x * EXPR_TILE + threadIdx.x;
+  const int lane = threadIdx.x & (WAVE - 1);
+  expr_regs<DEPTH> s;
+  #pragma unroll
+  for (int r = 0; r < EXPR_ITEMS; r++) {
+    #pragma unroll
+    for (int d = 0; d < DEPTH; d++) s.v[d][r] = 0;
+    s.nl[r] = 0; s.onull[r] = 0;
+  }
+  for (int pc = 0; pc < a.ninsns; pc++) expr_step<FULL, DEPTH>(s, a, pc, n, base, lane);
+}
+
+/* DEPTH slots: the host picks the EXPR_SHALLOW-slot kernel for a program whose
+ * stack never grows past it (Q1's needs 3), which halves the registers */
+template <int DEPTH>
+__global__ __launch_bounds__(EXPR_BLOCK)
+void k_expr_eval(int64_t n, expr_args a) {
+  if ((int64_t)(blockIdx.x + 1) * EXPR_TILE <= n) expr_run<true, DEPTH>(n, a);
+  else expr_run<false, DEPTH>(n, a);
+}
+#undef EXPR_BY_TYPE
+#undef EXPR_ROWS
+#undef EXPR_NL
+#undef EXPR_SET_NL
+
+static const char* expr_type_name(int t) {
+  return t == GPUQ_INT64 ? "int64" : t == GPUQ_FLOAT64 ? "float64"
+         : t == GPUQ_EXPR_BOOL ? "bool" : "?";
+}
+
+extern "C" int gpuq_project_expr(void* stream, int64_t n,
+                                 const gpuq_col* cols, int32_t ncols,
+                                 const gpuq_expr_insn* prog, int32_t ninsns,
+                                 void* const* outs, uint8_t* const* out_bits,
+                                 const int32_t* out_dtypes, int32_t nouts) {
+  hipStream_t s = (hipStream_t)stream;
+#define XFAIL(...) FAIL(GPUQ_ERR_INVALID, "project_expr: " __VA_ARGS__)
+  if (n < 0 || n > 0xFFFFFFFFLL) XFAIL("nrows %lld out of range", (long long)n);
+  if (ncols < 0 || ncols > GPUQ_EXPR_MAX_COLS)
+    XFAIL("%d columns, need 0..%d", ncols, GPUQ_EXPR_MAX_COLS);
+  if (ninsns < 1 || ninsns > GPUQ_EXPR_MAX_INSNS)
+    XFAIL("%d instructions, need 1..%d", ninsns, GPUQ_EXPR_MAX_INSNS);
+  if (nouts < 1 || nouts > GPUQ_EXPR_MAX_OUTS)
+    XFAIL("%d outputs, need 1..%d", nouts, GPUQ_EXPR_MAX_OUTS);
+  if ((ncols && !cols) || !prog || !outs || !out_dtypes)
+    XFAIL("missing argument array");
+  expr_args a;
+  memset(&a, 0, sizeof(a));
+  for (int c = 0; c < ncols; c++) {
+    if (cols[c].dtype != GPUQ_INT64 && cols[c].dtype != GPUQ_FLOAT64)
+      XFAIL("column %d has unsupported dtype %d", c, cols[c].dtype);
+    a.data[c] = cols[c].data;
+    a.validity[c] = cols[c].validity;
+  }
+  for (int k = 0; k < nouts; k++) {
+    if (out_dtypes[k] != GPUQ_INT64 && out_dtypes[k] != GPUQ_FLOAT64)
+      XFAIL("output %d has unsupported dtype %d", k, out_dtypes[k]);
+    a.out[k] = outs[k];
+    a.out_bits[k] = out_bits ? out_bits[k] : nullptr;
+  }
+  int ty[GPUQ_EXPR_MAX_DEPTH];
+  bool written[GPUQ_EXPR_MAX_OUTS] = {false, false, false, false};
+  int depth = 0, peak = 0;
+  for (int pc = 0; pc < ninsns; pc++) {
+    const gpuq_expr_insn& in = prog[pc];
+    const int dt = in.dtype;
+    int pops, push = -1;   /* push: the type pushed, -1 for none */
+    switch (in.opcode) {
+      case GPUQ_EXPR_COL: case GPUQ_EXPR_LIT: case GPUQ_EXPR_REF: pops = 0; break;
+      case GPUQ_EXPR_ARITH: case GPUQ_EXPR_CMP: case GPUQ_EXPR_AND:
+      case GPUQ_EXPR_OR: case GPUQ_EXPR_COALESCE: pops = 2; break;
+      case GPUQ_EXPR_SELECT: pops = 3; break;
+      case GPUQ_EXPR_NEG: case GPUQ_EXPR_ABS: case GPUQ_EXPR_CAST:
+      case GPUQ_EXPR_IS_NULL: case GPUQ_EXPR_IS_NOT_NULL: case GPUQ_EXPR_NOT:
+      case GPUQ_EXPR_OUT: pops = 1; break;
+      default: XFAIL("insn %d: bad opcode %d", pc, in.opcode);
+    }
+    if (depth < pops) XFAIL("insn %d: stack underflow", pc);
+    if (dt != GPUQ_INT64 && dt != GPUQ_FLOAT64 && dt != GPUQ_EXPR_BOOL)
+      XFAIL("insn %d: bad dtype %d", pc, dt);
+    const int top = pops >= 1 ? ty[depth - 1] : -1;
+    const int below = pops >= 2 ? ty[depth - 2] : -1;
+    const bool numeric = dt != GPUQ_EXPR_BOOL;
+    switch (in.opcode) {
+      case GPUQ_EXPR_COL:
+        if (in.arg < 0 || in.arg >= ncols)
+          XFAIL("insn %d: column index %d out of range", pc, in.arg);
+        if (dt != cols[in.arg].dtype)
+          XFAIL("insn %d: declared dtype %s, column %d is %s", pc,
+                expr_type_name(dt), in.arg, expr_type_name(cols[in.arg].dtype));
+        push = dt;
+        break;
+      case GPUQ_EXPR_LIT:
+        if (in.arg != 0 && in.arg != 1)
+          XFAIL("insn %d: bad NULL-literal flag %d", pc, in.arg);
+        if (dt == GPUQ_EXPR_BOOL && in.arg == 0 && in.lit_i64 != 0 && in.lit_i64 != 1)
+          XFAIL("insn %d: bad bool literal %lld", pc, (long long)in.lit_i64);
+        push = dt;
+        break;
+      case GPUQ_EXPR_REF:
+        if (in.arg < 0 || in.arg >= nouts)
+          XFAIL("insn %d: output index %d out of range", pc, in.arg);
+        if (!written[in.arg])
+          XFAIL("insn %d: REF to output %d, which is not yet written", pc, in.arg);
+        if (dt != out_dtypes[in.arg])
+          XFAIL("insn %d: declared dtype %s, output %d is %s", pc,
+                expr_type_name(dt), in.arg, expr_type_name(out_dtypes[in.arg]));
+        push = dt;
+        break;
+      case GPUQ_EXPR_ARITH:
+      case GPUQ_EXPR_CMP:
+        if (in.opcode == GPUQ_EXPR_ARITH && (in.arg < GPUQ_BINOP_ADD || in.arg > GPUQ_BINOP_DIV))
+          XFAIL("insn %d: bad binop %d", pc, in.arg);
+        if (in.opcode == GPUQ_EXPR_CMP && (in.arg < GPUQ_CMP_EQ || in.arg > GPUQ_CMP_NE))
+          XFAIL("insn %d: bad comparison %d", pc, in.arg);
+        if (top != below)
+          XFAIL("insn %d: operand types differ (%s vs %s)", pc,
+                expr_type_name(below), expr_type_name(top));
+        if (top == GPUQ_EXPR_BOOL) XFAIL("insn %d: bool operand to an arithmetic or comparison op", pc);
+        if (dt != top)
+          XFAIL("insn %d: declared dtype %s, operands are %s", pc,
+                expr_type_name(dt), expr_type_name(top));
+        push = in.opcode == GPUQ_EXPR_CMP ? GPUQ_EXPR_BOOL : dt;
+        break;
+      case GPUQ_EXPR_NEG:
+      case GPUQ_EXPR_ABS:
+        if (top == GPUQ_EXPR_BOOL) XFAIL("insn %d: bool operand to an arithmetic or comparison op", pc);
+        if (dt != top)
+          XFAIL("insn %d: declared dtype %s, operand is %s", pc,
+                expr_type_name(dt), expr_type_name(top));
+        push = dt;
+        break;
+      case GPUQ_EXPR_CAST:
+        if (!((dt == GPUQ_INT64 && in.arg == GPUQ_FLOAT64) ||
+              (dt == GPUQ_FLOAT64 && in.arg == GPUQ_INT64) ||
+              (dt == GPUQ_EXPR_BOOL && in.arg == GPUQ_INT64)))
+          XFAIL("insn %d: bad cast %s -> %s", pc, expr_type_name(dt), expr_type_name(in.arg));
+        if (dt != top)
+          XFAIL("insn %d: declared dtype %s, operand is %s", pc,
+                expr_type_name(dt), expr_type_name(top));
+        push = in.arg;
+        break;
+      case GPUQ_EXPR_IS_NULL:
+      case GPUQ_EXPR_IS_NOT_NULL:
+        if (dt != top)
+          XFAIL("insn %d: declared dtype %s, operand is %s", pc,
+                expr_type_name(dt), expr_type_name(top));
+        push = GPUQ_EXPR_BOOL;
+        break;
+      case GPUQ_EXPR_AND:
+      case GPUQ_EXPR_OR:
+        if (top != GPUQ_EXPR_BOOL || below != GPUQ_EXPR_BOOL)
+          XFAIL("insn %d: non-bool operand to AND / OR", pc);
+        if (numeric) XFAIL("insn %d: declared dtype %s, operands are bool", pc, expr_type_name(dt));
+        push = GPUQ_EXPR_BOOL;
+        break;
+      case GPUQ_EXPR_NOT:
+        if (top != GPUQ_EXPR_BOOL) XFAIL("insn %d: non-bool operand to NOT", pc);
+        if (numeric) XFAIL("insn %d: declared dtype %s, operand is bool", pc, expr_type_name(dt));
+        push = GPUQ_EXPR_BOOL;
+        break;
+      case GPUQ_EXPR_SELECT:
+        if (top != GPUQ_EXPR_BOOL) XFAIL("insn %d: non-bool SELECT condition", pc);
+        if (below != ty[depth - 3])
+          XFAIL("insn %d: operand types differ (%s vs %s)", pc,
+                expr_type_name(ty[depth - 3]), expr_type_name(below));
+        if (dt != below)
+          XFAIL("insn %d: declared dtype %s, operands are %s", pc,
+                expr_type_name(dt), expr_type_name(below));
+        push = dt;
+        break;
+      case GPUQ_EXPR_COALESCE:
+        if (top != below)
+          XFAIL("insn %d: operand types differ (%s vs %s)", pc,
+                expr_type_name(below), expr_type_name(top));
+        if (dt != top)
+          XFAIL("insn %d: declared dtype %s, operands are %s", pc,
+                expr_type_name(dt), expr_type_name(top));
+        push = dt;
+        break;
+      default:   /* OUT */
+        if (in.arg < 0 || in.arg >= nouts)
+          XFAIL("insn %d: output index %d out of range", pc, in.arg);
+        if (written[in.arg]) XFAIL("insn %d: output %d written twice", pc, in.arg);
+        if (top == GPUQ_EXPR_BOOL) XFAIL("insn %d: bool operand to OUT (cast it to int64)", pc);
+        if (dt != top || dt != out_dtypes[in.arg])
+          XFAIL("insn %d: declared dtype %s, operand is %s, output %d is %s", pc,
+                expr_type_name(dt), expr_type_name(top), in.arg,
+                expr_type_name(out_dtypes[in.arg]));
+        written[in.arg] = true;
+        break;
+    }
+    a.insn[pc] = in;
+    a.insn[pc].pad = depth;
+    depth -= pops;
+    if (push >= 0) {
+      if (depth >= GPUQ_EXPR_MAX_DEPTH)
+        XFAIL("insn %d: stack depth exceeds %d", pc, GPUQ_EXPR_MAX_DEPTH);
+      ty[depth++] = push;
+      if (depth > peak) peak = depth;
+    }
+  }
+  if (depth != 0) XFAIL("program leaves %d values on the stack, need 0", depth);
+  for (int k = 0; k < nouts; k++)
+    if (!written[k]) XFAIL("output %d is never written", k);
+  if (n == 0) return GPUQ_OK;
+  for (int k = 0; k < nouts; k++)
+    if (!outs[k]) XFAIL("output %d has no buffer", k);
+  for (int c = 0; c < ncols; c++)
+    if (!cols[c].data) XFAIL("column %d has no buffer", c);
+#undef XFAIL
+  a.ninsns = ninsns;
+  const int64_t nb = (n + EXPR_TILE - 1) / EXPR_TILE;
+  { hipEvent_t _pe = prof_begin(s);
+  if (peak <= EXPR_SHALLOW)
+    k_expr_eval<EXPR_SHALLOW><<<dim3((uint32_t)nb), EXPR_BLOCK, 0, s>>>(n, a);
+  else
+    k_expr_eval<GPUQ_EXPR_MAX_DEPTH><<<dim3((uint32_t)nb), EXPR_BLOCK, 0, s>>>(n, a);
+  prof_end("project_expr", s, _pe); }
+  HIP_TRY(hipGetLastError());
+  return GPUQ_OK;
+}
+
 /* int64 -> float64 cast (AVG = SUM/COUNT evaluation; Average.scala
  * evaluateExpression divides sum by count cast to double) */
 __global__ void k_cast_i64_f64(int64_t n, const int64_t* in, double* out) {

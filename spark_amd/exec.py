@@ -18,6 +18,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from . import expression
 from .predicate import (And, Between, Cmp, Col, In, IsNotNull,  # noqa: F401
                         IsNull, Not, Or, Pred)
 
@@ -353,8 +354,14 @@ class FilterExec(_CpuNode):
         return self.children[0].output
 
 
+def _is_expr_entry(p) -> bool:
+    """(out_name, expr): the expression form of a projection entry"""
+    return isinstance(p, tuple) and len(p) == 2 and expression.is_expr(p[1])
+
+
 class ProjectExec(_CpuNode):
-    """projections: list of (out_name, a, op, b_or_None, literal_or_None) plus
+    """projections: list of (out_name, a, op, b_or_None, literal_or_None),
+    (out_name, expr) with an expression tree of spark_amd.expression, plus
     pass-through column names."""
 
     def __init__(self, projections, child):
@@ -1635,15 +1642,45 @@ class GpuFilterExec(SparkPlan):
 
 
 class GpuProjectExec(SparkPlan):
-    """Replaces ProjectExec for elementwise binary
-    arithmetic; pass-through entries keep their column and its validity
-    bitmap. A computed row is NULL iff an input row is NULL or the op is a
-    division by zero (Spark non-ANSI); its column carries a bitmap unless
-    nothing can be NULL (no input bitmap and op is not `/`)."""
+    """Replaces ProjectExec; pass-through entries keep their
+    column and its validity bitmap. A 5-tuple entry is one binary operation
+    through gpuq_project_binop_nullable: its row is NULL iff an input row is
+    NULL or the op is a division by zero (Spark non-ANSI). All (out_name,
+    expr) entries of the node are evaluated together by one
+    gpuq_project_expr call per batch (more only if they exceed that call's
+    output, column, instruction or depth caps), each input column read once.
+    A computed column carries a bitmap unless nothing in it can be NULL."""
 
     def __init__(self, projections, child):
         super().__init__(child)
         self.projections = projections
+        self._lowered = {}      # (schema, nullable columns) -> chunks
+
+    def _expr_chunks(self, batch):
+        """the node's expression entries lowered for this batch's schema:
+        [(out_names, lowered program tuple)], one gpuq_project_expr call each"""
+        entries = [p for p in self.projections if _is_expr_entry(p)]
+        if not entries:
+            return []
+        cols = batch.columns()
+        nullable = tuple(k for k in cols if batch.validity(k) is not None)
+        key = (tuple((k, str(t.dtype)) for k, t in cols.items()), nullable)
+        if key not in self._lowered:
+            schema = {k: t.dtype for k, t in cols.items()}
+            chunks, cur, cur_low = [], [], None
+            for ent in entries:
+                try:
+                    low = expression.lower(cur + [ent], schema, nullable)
+                except ValueError:
+                    if not cur:
+                        raise
+                    chunks.append(([n for n, _ in cur], cur_low))
+                    cur = []
+                    low = expression.lower([ent], schema, nullable)
+                cur, cur_low = cur + [ent], low
+            chunks.append(([n for n, _ in cur], cur_low))
+            self._lowered[key] = chunks
+        return self._lowered[key]
 
     @property
     def output(self):
@@ -1657,10 +1694,20 @@ class GpuProjectExec(SparkPlan):
         from . import gpuq
         for batch in self.children[0].execute_columnar():
             cols, validity = {}, {}
+            computed = {}
+            for out_names, low in self._expr_chunks(batch):
+                in_cols = batch.columns()
+                computed.update(gpuq.project_expr_program(
+                    in_cols, low[0], low[1], out_names, low[2], low[3],
+                    validities={k: batch.validity(k) for k in low[0]
+                                if batch.validity(k) is not None}))
             for p in self.projections:
                 if isinstance(p, str):
                     cols[p] = batch.column(p)
                     v = batch.validity(p)
+                elif _is_expr_entry(p):
+                    p = p[0]
+                    cols[p], v = computed[p]
                 else:
                     out_name, a, op, b, lit = p
                     p = out_name

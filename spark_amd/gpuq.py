@@ -11,7 +11,7 @@ import os
 
 import torch
 
-from . import predicate
+from . import expression, predicate
 from .predicate import rewrite_i64_float_cmp
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
@@ -43,6 +43,15 @@ class _PredInsn(ctypes.Structure):
                 ("cmp", ctypes.c_int32),
                 ("col_a", ctypes.c_int32),
                 ("col_b", ctypes.c_int32),
+                ("lit_i64", ctypes.c_int64),
+                ("lit_f64", ctypes.c_double)]
+
+
+class _ExprInsn(ctypes.Structure):
+    _fields_ = [("opcode", ctypes.c_int32),
+                ("arg", ctypes.c_int32),
+                ("dtype", ctypes.c_int32),
+                ("pad", ctypes.c_int32),
                 ("lit_i64", ctypes.c_int64),
                 ("lit_f64", ctypes.c_double)]
 
@@ -185,6 +194,11 @@ def lib() -> ctypes.CDLL:
         L.gpuq_project_binop_nullable.argtypes = [vp, i64, _Col, _Col,
                                                   ctypes.c_double, i64, i32,
                                                   vp, vp]
+        L.gpuq_project_expr.restype = i32
+        L.gpuq_project_expr.argtypes = [vp, i64, ctypes.POINTER(_Col), i32,
+                                        ctypes.POINTER(_ExprInsn), i32,
+                                        ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                        ctypes.POINTER(i32), i32]
         L.gpuq_range_i64.restype = i32
         L.gpuq_sort_last_plan.restype = None
         L.gpuq_sort_last_plan.argtypes = [ctypes.POINTER(ctypes.c_int)] * 3
@@ -697,6 +711,72 @@ def project_binop_nullable(a: torch.Tensor, op: str, b=None, literal=None,
         _stream(), n, _col(a, a_validity), bcol, lit_f, lit_i, BINOP[op],
         out.data_ptr(), _dp(bits)))
     return out, bits
+
+
+EXPR_TILE = 1024          # rows per block of k_expr_eval
+EXPR_MAX_INSNS = expression.MAX_INSNS
+EXPR_MAX_COLS = expression.MAX_COLS
+EXPR_MAX_OUTS = expression.MAX_OUTS
+EXPR_MAX_DEPTH = expression.MAX_DEPTH
+
+_EXPR_TORCH = {"i64": torch.int64, "f64": torch.float64}
+
+
+def project_expr_program(columns: dict, names, prog, out_names, out_dtypes,
+                         out_nullable, validities: dict = None):
+    """Run an already lowered program (the tuple expression.lower returns,
+    plus the output names) in one gpuq_project_expr call. Returns
+    {out_name: (tensor, bitmap or None)}; an output gets a bitmap only where
+    out_nullable says it can hold a NULL."""
+    validities = validities or {}
+    if not columns:
+        raise ValueError("project_expr: needs a column to take the row "
+                         "count and device from")
+    any_col = next(iter(columns.values()))
+    n, dev = any_col.numel(), any_col.device
+    for name in names:
+        if columns[name].numel() != n:
+            raise ValueError(f"project_expr: column {name!r} has "
+                             f"{columns[name].numel()} rows, expected {n}")
+    cols_arr = (_Col * max(len(names), 1))(
+        *[_col(columns[k], validities.get(k)) for k in names])
+    prog_arr = (_ExprInsn * max(len(prog), 1))(
+        *[_ExprInsn(*insn) for insn in prog])
+    nouts = len(out_names)
+    outs = [torch.empty(n, dtype=_EXPR_TORCH[dt], device=dev)
+            for dt in out_dtypes]
+    bits = [torch.empty(_bitmap_bytes(n), dtype=torch.uint8, device=dev)
+            if nl else None for nl in out_nullable]
+    vp = ctypes.c_void_p
+    outs_arr = (vp * max(nouts, 1))(*[t.data_ptr() for t in outs])
+    bits_arr = (vp * max(nouts, 1))(*[_dp(b) for b in bits])
+    dt_arr = (ctypes.c_int32 * max(nouts, 1))(
+        *[expression.TYPE_CODE[dt] for dt in out_dtypes])
+    _check(lib().gpuq_project_expr(_stream(), n, cols_arr, len(names),
+                                   prog_arr, len(prog), outs_arr, bits_arr,
+                                   dt_arr, nouts))
+    return {name: (t, b) for name, t, b in zip(out_names, outs, bits)}
+
+
+def project_expr(columns: dict, outputs, validities: dict = None):
+    """Compound SELECT-list expressions (spark_amd.expression: arithmetic
+    trees, Neg / Abs, Cast, comparisons as values, If / CaseWhen, Coalesce) in
+    one fused pass: every referenced column is read once, up to EXPR_MAX_OUTS
+    outputs are written. outputs is an ordered [(name, expr)] list; a later
+    output that contains the whole tree of an earlier one reuses its value.
+    Returns {name: (tensor, bitmap or None)}; the bitmap is None where nothing
+    in the expression can be NULL.
+
+    columns maps name -> tensor (all of one length; only the columns the
+    expressions name are read), validities name -> validity bitmap."""
+    validities = validities or {}
+    outputs = list(outputs)
+    names, prog, out_dtypes, out_nullable = expression.lower(
+        outputs, {k: t.dtype for k, t in columns.items()},
+        nullable=[k for k in columns if validities.get(k) is not None])
+    return project_expr_program(columns, names, prog,
+                                [name for name, _ in outputs], out_dtypes,
+                                out_nullable, validities)
 
 
 def cast_i64_f64(t: torch.Tensor) -> torch.Tensor:
