@@ -436,6 +436,67 @@ int gpuq_join_probe_keys(void* stream, int64_t probe_rows,
                          uint32_t* out_probe_rid, uint32_t* out_build_rid,
                          int64_t out_capacity, int64_t* out_nmatches);
 
+/* Probe with a residual join condition — the non-equi remainder of the ON
+ * clause that HashJoin.scala keeps as boundCondition (`l.k = r.k AND
+ * l.ship < r.cutoff`: the equality is the key, the rest is the condition).
+ * Same table (gpuq_join_build_keys), same workspace and same pair output as
+ * gpuq_join_probe_keys; no new build, and gpuq_join_keys_unmatched_build is
+ * used unchanged.
+ *
+ * cond_cols[ncond_cols] are the columns the condition reads; cond_sides[c]
+ * says which side cond_cols[c] belongs to: a probe-side column is indexed by
+ * the probe row id, a build-side column by the build row id. prog is exactly
+ * a gpuq_filter_expr program over cond_cols (HOST array, copied into the
+ * kernel arguments): the same eight opcodes, the same GPUQ_PRED_MAX_* caps,
+ * the same comparison rules (total order on float64, -0.0 == 0.0, NaN == NaN
+ * and greatest) and the same Kleene tables. CMP_COL may compare a probe
+ * column with a build column of equal dtype.
+ *
+ * A candidate pair (all keys equal, no NULL in any key column) PASSES iff
+ * the program evaluates to TRUE for it; FALSE and NULL both fail. The join
+ * types are those of gpuq_join_probe_keys with "match" read as "passing
+ * pair":
+ *   0 Inner      every passing pair;
+ *   1 Outer      every passing pair; a probe row without one — NULL key, no
+ *                key match, or a key match whose candidates all fail — emits
+ *                (i, 0xFFFFFFFF) once;
+ *   2 LeftSemi   the probe row once iff at least one pair passes;
+ *   3 LeftAnti   the probe row once iff no pair passes (NULL-key rows and
+ *                rows whose candidates all fail included);
+ *   4 FullOuter  probe half: as 1, and sets the matched bit of exactly the
+ *                build rows that appear in a passing pair. Key-equal build
+ *                rows whose pairs all fail stay unmatched and come out of
+ *                gpuq_join_keys_unmatched_build;
+ *   5            GPUQ_ERR_INVALID: Spark requires an empty condition for the
+ *                null-aware anti join.
+ * As for gpuq_join_probe_keys: *out_nmatches is always set; if it exceeds
+ * out_capacity nothing is written past out_capacity and GPUQ_ERR_OVERFLOW is
+ * returned (call again with bigger buffers; setting matched bits twice is
+ * harmless); emission order is nondeterministic; probe_rows == 0 launches
+ * nothing.
+ * Returned as GPUQ_ERR_INVALID before anything is launched: everything
+ * gpuq_join_probe_keys rejects; ncond_cols outside 1..GPUQ_PRED_MAX_COLS; a
+ * NULL cond_cols, cond_sides or prog; a side other than 0 or 1; ninsns
+ * outside 1..GPUQ_PRED_MAX_INSNS; and every program error gpuq_filter_expr
+ * rejects — a bad opcode, comparison code or CONST value, a column index out
+ * of range, a column whose dtype is not int64 / float64, CMP_COL over two
+ * dtypes, a stack that underflows, grows past GPUQ_PRED_MAX_DEPTH or does
+ * not end at depth exactly 1. */
+#define GPUQ_JOIN_SIDE_PROBE 0
+#define GPUQ_JOIN_SIDE_BUILD 1
+
+struct gpuq_pred_insn;   /* defined with gpuq_filter_expr below */
+
+int gpuq_join_probe_keys_cond(void* stream, int64_t probe_rows,
+                              const gpuq_col* probe_keys, int32_t nkeys,
+                              void* workspace, int64_t capacity, int64_t build_rows,
+                              int32_t join_type,
+                              const gpuq_col* cond_cols, const int32_t* cond_sides,
+                              int32_t ncond_cols,
+                              const struct gpuq_pred_insn* prog /* HOST */, int32_t ninsns,
+                              uint32_t* out_probe_rid, uint32_t* out_build_rid,
+                              int64_t out_capacity, int64_t* out_nmatches);
+
 /* FullOuter second half: one (0xFFFFFFFF, build_rid) pair per build row
  * whose matched bit is clear after the type-4 probes so far — NULL-key
  * build rows included (never inserted, so never matched). Same overflow

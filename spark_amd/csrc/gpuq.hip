@@ -5432,6 +5432,57 @@ extern "C" int64_t gpuq_filter_expr_workspace_bytes(int64_t n) {
   return total;
 }
 
+/* Column dtypes and the postfix program, checked on the host before anything
+ * is launched: shared by gpuq_filter_expr and gpuq_join_probe_keys_cond
+ * (`who` prefixes the messages). The caller has checked ncols and ninsns
+ * against the caps. */
+static int pred_check_program(const char* who, const gpuq_col* cols, int32_t ncols,
+                              const gpuq_pred_insn* prog, int32_t ninsns) {
+  for (int c = 0; c < ncols; c++)
+    if (cols[c].dtype != GPUQ_INT64 && cols[c].dtype != GPUQ_FLOAT64)
+      FAIL(GPUQ_ERR_INVALID, "%s: column %d has unsupported dtype %d", who, c, cols[c].dtype);
+  int depth = 0;
+  for (int pc = 0; pc < ninsns; pc++) {
+    const gpuq_pred_insn& in = prog[pc];
+    int pops = 0;
+    switch (in.opcode) {
+      case GPUQ_PRED_CMP_COL:
+        if (in.col_b < 0 || in.col_b >= ncols)
+          FAIL(GPUQ_ERR_INVALID, "%s: insn %d: column index %d out of range", who, pc, in.col_b);
+        /* fallthrough */
+      case GPUQ_PRED_CMP_LIT:
+        if (in.cmp < GPUQ_CMP_EQ || in.cmp > GPUQ_CMP_NE)
+          FAIL(GPUQ_ERR_INVALID, "%s: insn %d: bad comparison %d", who, pc, in.cmp);
+        /* fallthrough */
+      case GPUQ_PRED_IS_NULL:
+      case GPUQ_PRED_IS_NOT_NULL:
+        if (in.col_a < 0 || in.col_a >= ncols)
+          FAIL(GPUQ_ERR_INVALID, "%s: insn %d: column index %d out of range", who, pc, in.col_a);
+        if (in.opcode == GPUQ_PRED_CMP_COL && cols[in.col_a].dtype != cols[in.col_b].dtype)
+          FAIL(GPUQ_ERR_INVALID, "%s: insn %d: column dtypes differ (%d vs %d)", who, pc,
+               cols[in.col_a].dtype, cols[in.col_b].dtype);
+        break;
+      case GPUQ_PRED_CONST:
+        if (in.cmp < GPUQ_PRED_FALSE || in.cmp > GPUQ_PRED_NULL)
+          FAIL(GPUQ_ERR_INVALID, "%s: insn %d: bad constant %d", who, pc, in.cmp);
+        break;
+      case GPUQ_PRED_AND:
+      case GPUQ_PRED_OR: pops = 2; break;
+      case GPUQ_PRED_NOT: pops = 1; break;
+      default:
+        FAIL(GPUQ_ERR_INVALID, "%s: insn %d: bad opcode %d", who, pc, in.opcode);
+    }
+    if (depth < pops)
+      FAIL(GPUQ_ERR_INVALID, "%s: insn %d: stack underflow", who, pc);
+    depth += 1 - pops;
+    if (depth > GPUQ_PRED_MAX_DEPTH)
+      FAIL(GPUQ_ERR_INVALID, "%s: insn %d: stack depth exceeds %d", who, pc, GPUQ_PRED_MAX_DEPTH);
+  }
+  if (depth != 1)
+    FAIL(GPUQ_ERR_INVALID, "%s: program leaves %d values on the stack, need 1", who, depth);
+  return GPUQ_OK;
+}
+
 extern "C" int gpuq_filter_expr(void* stream, int64_t n,
                                 const gpuq_col* cols, int32_t ncols,
                                 const gpuq_pred_insn* prog, int32_t ninsns,
@@ -5444,55 +5495,15 @@ extern "C" int gpuq_filter_expr(void* stream, int64_t n,
     FAIL(GPUQ_ERR_INVALID, "filter_expr: %d columns, need 0..%d", ncols, GPUQ_PRED_MAX_COLS);
   if (ninsns < 1 || ninsns > GPUQ_PRED_MAX_INSNS)
     FAIL(GPUQ_ERR_INVALID, "filter_expr: %d instructions, need 1..%d", ninsns, GPUQ_PRED_MAX_INSNS);
+  if (int rc = pred_check_program("filter_expr", cols, ncols, prog, ninsns)) return rc;
   pred_args a;
   memset(&a, 0, sizeof(a));
   for (int c = 0; c < ncols; c++) {
-    if (cols[c].dtype != GPUQ_INT64 && cols[c].dtype != GPUQ_FLOAT64)
-      FAIL(GPUQ_ERR_INVALID, "filter_expr: column %d has unsupported dtype %d", c, cols[c].dtype);
     a.data[c] = cols[c].data;
     a.validity[c] = cols[c].validity;
     a.dtype[c] = cols[c].dtype;
   }
-  int depth = 0;
-  for (int pc = 0; pc < ninsns; pc++) {
-    const gpuq_pred_insn& in = prog[pc];
-    int pops = 0;
-    switch (in.opcode) {
-      case GPUQ_PRED_CMP_COL:
-        if (in.col_b < 0 || in.col_b >= ncols)
-          FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: column index %d out of range", pc, in.col_b);
-        /* fallthrough */
-      case GPUQ_PRED_CMP_LIT:
-        if (in.cmp < GPUQ_CMP_EQ || in.cmp > GPUQ_CMP_NE)
-          FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: bad comparison %d", pc, in.cmp);
-        /* fallthrough */
-      case GPUQ_PRED_IS_NULL:
-      case GPUQ_PRED_IS_NOT_NULL:
-        if (in.col_a < 0 || in.col_a >= ncols)
-          FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: column index %d out of range", pc, in.col_a);
-        if (in.opcode == GPUQ_PRED_CMP_COL && cols[in.col_a].dtype != cols[in.col_b].dtype)
-          FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: column dtypes differ (%d vs %d)", pc,
-               cols[in.col_a].dtype, cols[in.col_b].dtype);
-        break;
-      case GPUQ_PRED_CONST:
-        if (in.cmp < GPUQ_PRED_FALSE || in.cmp > GPUQ_PRED_NULL)
-          FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: bad constant %d", pc, in.cmp);
-        break;
-      case GPUQ_PRED_AND:
-      case GPUQ_PRED_OR: pops = 2; break;
-      case GPUQ_PRED_NOT: pops = 1; break;
-      default:
-        FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: bad opcode %d", pc, in.opcode);
-    }
-    if (depth < pops)
-      FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: stack underflow", pc);
-    depth += 1 - pops;
-    if (depth > GPUQ_PRED_MAX_DEPTH)
-      FAIL(GPUQ_ERR_INVALID, "filter_expr: insn %d: stack depth exceeds %d", pc, GPUQ_PRED_MAX_DEPTH);
-    a.insn[pc] = in;
-  }
-  if (depth != 1)
-    FAIL(GPUQ_ERR_INVALID, "filter_expr: program leaves %d values on the stack, need 1", depth);
+  for (int pc = 0; pc < ninsns; pc++) a.insn[pc] = prog[pc];
   a.ninsns = ninsns;
   pred_ws w; int64_t need;
   pred_ws_layout(n, &w, (char*)workspace, &need);
@@ -5514,6 +5525,307 @@ extern "C" int gpuq_filter_expr(void* stream, int64_t n,
       w.mask, w.scan, (uint32_t)nb, out_perm, (unsigned long long*)out_count);
   prof_end("filter_expr_emit", s, _pe); }
   HIP_TRY(hipGetLastError());
+  return GPUQ_OK;
+}
+
+/* ---- composite-key join: residual condition inside the probe ----
+ * (gpuq_join_probe_keys_cond; it sits here, not beside k_joink_probe, because
+ * it interprets the predicate program defined above.)
+ *
+ * k_joink_probe's two phases over the same table, with "match" narrowed to
+ * "candidate for which the program is TRUE": phase A walks each probe row's
+ * chain, evaluates the program on every (probe row, build row) candidate,
+ * counts the passing ones and keeps the first two passing build rows in
+ * c0 / c1; one output reservation per block; phase B emits, and for a row
+ * with more than two passing pairs walks the rest of its chain again, from
+ * next[c1] on, re-evaluating the program. Both walks follow next[] over an
+ * immutable table and read the same columns, so phase B finds exactly the
+ * cnt - 2 passing candidates phase A counted after c1.
+ *
+ * Blocks own JOINC_CHUNK = 1024 rows (4 rounds), not JOIN_CHUNK: the rounds
+ * are unrolled so that cnt / c0 / c1 stay in registers, and each round now
+ * carries two copies of the interpreter. One cursor atomicAdd per 1024 probe
+ * rows is still negligible.
+ *
+ * The program and the column table arrive by value in the kernel arguments,
+ * so the program counter and every column index are wave-uniform even though
+ * the lanes of a wave sit at different depths of different chains. The
+ * evaluation stack is k_pred_mask's pair of bit words, and nothing is
+ * indexed by a runtime value. A leaf loads its operand for the pair at hand:
+ * a build-side column at the build row (one random 8-byte load), a
+ * probe-side column at the probe row (coalesced across the wave, and served
+ * by the L1 from the row's second candidate on). A one-entry cache makes the
+ * leaves of an IN / BETWEEN on one column load it once per candidate.
+ * Holding the probe-side operands of a row in registers instead was tried:
+ * with up to GPUQ_PRED_MAX_COLS columns they form an array that a leaf has
+ * to pick from by its (uniform, but runtime) column index, which the
+ * compiler turns into an indexed private array and parks in LDS — 18 KB per
+ * block and an LDS round trip per leaf — so the loads stayed. */
+#define JOINC_CHUNK 1024
+
+struct joinc_args {
+  const void* data[GPUQ_PRED_MAX_COLS];
+  const uint8_t* validity[GPUQ_PRED_MAX_COLS];
+  int32_t dtype[GPUQ_PRED_MAX_COLS];
+  int32_t side[GPUQ_PRED_MAX_COLS];   /* GPUQ_JOIN_SIDE_* */
+  int32_t ncols;
+  int32_t ninsns;
+  gpuq_pred_insn insn[GPUQ_PRED_MAX_INSNS];
+};
+
+/* column c's value and validity for the pair (probe row i, build row b); the
+ * side is wave-uniform, the row index a select between two registers */
+DEV void joinc_operand(const joinc_args& a, int64_t i, unsigned int b, int c,
+                       uint64_t* x, uint32_t* ok) {
+  const int64_t row = a.side[c] == GPUQ_JOIN_SIDE_BUILD ? (int64_t)b : i;
+  *x = ((const uint64_t*)a.data[c])[row];
+  *ok = bit_valid(a.validity[c], row);
+}
+
+DEV uint32_t joinc_cmp(int dtype, uint64_t x, int op, uint64_t y) {
+  return dtype == GPUQ_FLOAT64
+      ? filter_cmp_f64(__longlong_as_double((long long)x), op,
+                       __longlong_as_double((long long)y))
+      : filter_cmp_i64((int64_t)x, op, (int64_t)y);
+}
+
+/* TRUE iff the program evaluates to TRUE for (probe row i, build row b).
+ * Bit d of tb / nb is the TRUE / NULL flag of stack slot d, as in
+ * k_pred_mask; the validated program never pops an empty stack. */
+DEV bool joinc_pass(const joinc_args& a, int64_t i, unsigned int b) {
+  uint32_t tb = 0, nb = 0;
+  uint64_t cv = 0;
+  uint32_t cok = 0;
+  int cached = -1;
+  for (int pc = 0; pc < a.ninsns; pc++) {
+    const int opcode = a.insn[pc].opcode;
+    if (opcode <= GPUQ_PRED_IS_NOT_NULL) {
+      const int ca = a.insn[pc].col_a;
+      if (ca != cached) {
+        joinc_operand(a, i, b, ca, &cv, &cok);
+        cached = ca;
+      }
+      if (opcode == GPUQ_PRED_CMP_LIT) {
+        const uint64_t lit = a.dtype[ca] == GPUQ_FLOAT64
+            ? (uint64_t)__double_as_longlong(a.insn[pc].lit_f64)
+            : (uint64_t)a.insn[pc].lit_i64;
+        uint32_t t = joinc_cmp(a.dtype[ca], cv, a.insn[pc].cmp, lit);
+        tb = (tb << 1) | (t & cok);
+        nb = (nb << 1) | (cok ^ 1);
+      } else if (opcode == GPUQ_PRED_CMP_COL) {
+        uint64_t y; uint32_t yok;
+        joinc_operand(a, i, b, a.insn[pc].col_b, &y, &yok);
+        yok &= cok;
+        uint32_t t = joinc_cmp(a.dtype[ca], cv, a.insn[pc].cmp, y);
+        tb = (tb << 1) | (t & yok);
+        nb = (nb << 1) | (yok ^ 1);
+      } else {   /* IS_NULL / IS_NOT_NULL */
+        const uint32_t flip = opcode == GPUQ_PRED_IS_NULL ? 1u : 0u;
+        tb = (tb << 1) | (cok ^ flip);
+        nb = nb << 1;
+      }
+    } else if (opcode == GPUQ_PRED_CONST) {
+      tb = (tb << 1) | (uint32_t)(a.insn[pc].cmp == GPUQ_PRED_TRUE);
+      nb = (nb << 1) | (uint32_t)(a.insn[pc].cmp == GPUQ_PRED_NULL);
+    } else if (opcode == GPUQ_PRED_AND) {
+      uint32_t T = tb, N = nb;
+      uint32_t rt = (T >> 1) & T & 1;
+      /* NULL unless a side is FALSE: both sides TRUE-or-NULL, one NULL */
+      uint32_t rn = ((N >> 1) | N) & ((T >> 1) | (N >> 1)) & (T | N) & 1;
+      tb = ((T >> 1) & ~1u) | rt;
+      nb = ((N >> 1) & ~1u) | rn;
+    } else if (opcode == GPUQ_PRED_OR) {
+      uint32_t T = tb, N = nb;
+      uint32_t rt = ((T >> 1) | T) & 1;
+      uint32_t rn = ((N >> 1) | N) & ~rt & 1;
+      tb = ((T >> 1) & ~1u) | rt;
+      nb = ((N >> 1) & ~1u) | rn;
+    } else {   /* NOT: FALSE <-> TRUE, NULL stays */
+      tb = (tb & ~1u) | (~(tb | nb) & 1);
+    }
+  }
+  return tb & 1;
+}
+
+/* JT 0-4 as k_joink_probe. Semi / anti need only "does a pair pass", so
+ * their chain walk stops at the first passing candidate. */
+template <int JT>
+__global__ __launch_bounds__(256)
+void k_joink_probe_cond(int64_t n, joink_cols kc, int nkeys, int sw,
+                        const unsigned long long* slots, const unsigned int* next,
+                        joink_sp* sp, int64_t cap_mask, joinc_args a,
+                        uint32_t* out_p, uint32_t* out_b, int64_t out_cap,
+                        unsigned long long* matched) {
+  constexpr int ROUNDS = JOINC_CHUNK / 256;
+  __shared__ unsigned long long block_base;
+  __shared__ uint32_t wtot[256 / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int64_t base = (int64_t)blockIdx.x * JOINC_CHUNK;
+
+  uint32_t cnt[ROUNDS];
+  unsigned int c0[ROUNDS], c1[ROUNDS];
+  uint32_t lane_total = 0;
+  #pragma unroll
+  for (int r = 0; r < ROUNDS; r++) {
+    int64_t i = base + r * 256 + threadIdx.x;
+    unsigned int head = JOIN_NIL;
+    int64_t key[JOINK_MAX_KEYS];
+    uint32_t h; unsigned long long mysig;
+    if (i < n && joink_load(kc, nkeys, i, key, &h, &mysig)) {
+      uint64_t slot = h & (uint64_t)cap_mask;
+      /* bounded: a full table ends the walk after cap visits */
+      for (int64_t visits = 0; visits <= cap_mask; visits++) {
+        const unsigned long long* sl = slots + slot * sw;
+        unsigned long long cur = sl[0];
+        if (cur == JOINK_EMPTY) break;
+        if (cur == mysig) {
+          bool eq = true;
+#pragma unroll
+          for (int c = 0; c < JOINK_MAX_KEYS; c++)
+            if (c < nkeys) eq = eq && sl[2 + c] == (unsigned long long)key[c];
+          if (eq) { head = (unsigned int)sl[1]; break; }
+        }
+        slot = (slot + 1) & (uint64_t)cap_mask;
+      }
+    }
+    cnt[r] = 0; c0[r] = JOIN_NIL; c1[r] = JOIN_NIL;
+    /* a head without JOIN_MULTI is a one-candidate chain: next[] untouched */
+    const bool multi = head != JOIN_NIL && (head & JOIN_MULTI);
+    for (unsigned int b = head == JOIN_NIL ? JOIN_NIL : (head & ~JOIN_MULTI);
+         b != JOIN_NIL; b = multi ? next[b] : JOIN_NIL) {
+      if (!joinc_pass(a, i, b)) continue;
+      if (cnt[r] == 0) c0[r] = b; else if (cnt[r] == 1) c1[r] = b;
+      cnt[r]++;
+      if (JT == 4) atomicOr(&matched[b >> 6], 1ull << (b & 63));
+      if (JT == 2 || JT == 3) break;
+    }
+    if (JT == 0) lane_total += cnt[r];
+    else if (i < n) lane_total += jt_emit_count(JT, cnt[r]);
+  }
+  /* phase B: block-level reservation (emit order within the block is
+   * arbitrary — join output order is nondeterministic by contract) */
+  uint32_t incl = wave_inclusive_scan(lane_total);
+  if (lane == WAVE - 1) wtot[wave] = incl;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (int w = 0; w < 256 / WAVE; w++) {
+      uint32_t t = wtot[w]; wtot[w] = tot; tot += t;
+    }
+    block_base = tot ? atomicAdd(&sp->j.cursor, (unsigned long long)tot) : 0;
+  }
+  __syncthreads();
+  int64_t o = (int64_t)block_base + wtot[wave] + (incl - lane_total);
+  #pragma unroll
+  for (int r = 0; r < ROUNDS; r++) {
+    int64_t i = base + r * 256 + threadIdx.x;
+    if (JT != 0) {
+      if (i >= n || !jt_emit_count(JT, cnt[r])) continue;
+      if (JT == 2 || JT == 3 || cnt[r] == 0) {
+        /* semi/anti emit the probe row once; outer's row without a passing
+         * pair goes with NIL (NULL build columns downstream) */
+        if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = JOIN_NIL; }
+        o++;
+        continue;
+      }
+    }
+    if (!cnt[r]) continue;
+    if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = c0[r]; }
+    o++;
+    if (cnt[r] >= 2) {
+      if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = c1[r]; }
+      o++;
+    }
+    if (cnt[r] > 2) {
+      /* the candidates after c1, in phase A's order; o advances by the
+       * reserved cnt - 2 whatever the walk finds */
+      const int64_t o_end = o + (cnt[r] - 2);
+      for (unsigned int b = next[c1[r]]; b != JOIN_NIL && o < o_end; b = next[b]) {
+        if (!joinc_pass(a, i, b)) continue;
+        if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = b; }
+        o++;
+      }
+      o = o_end;
+    }
+  }
+}
+
+extern "C" int gpuq_join_probe_keys_cond(void* stream, int64_t prows,
+                                         const gpuq_col* probe_keys, int32_t nkeys,
+                                         void* workspace, int64_t cap, int64_t brows,
+                                         int32_t join_type,
+                                         const gpuq_col* cond_cols,
+                                         const int32_t* cond_sides, int32_t ncond_cols,
+                                         const gpuq_pred_insn* prog, int32_t ninsns,
+                                         uint32_t* out_p, uint32_t* out_b,
+                                         int64_t out_cap, int64_t* out_nmatches) {
+  hipStream_t s = (hipStream_t)stream;
+  const char* who = "join_keys probe_cond";
+  if (int rc = joink_check_table(who, nkeys, cap, brows)) return rc;
+  if (join_type == 5)
+    FAIL(GPUQ_ERR_INVALID, "%s: the null-aware anti join (type 5) takes no "
+         "condition", who);
+  if (join_type < 0 || join_type > 4)
+    FAIL(GPUQ_ERR_INVALID, "%s: bad join_type %d", who, join_type);
+  if (prows < 0 || prows > 0xFFFFFFFELL)
+    FAIL(GPUQ_ERR_INVALID, "%s: probe rows %lld do not fit 32-bit rowids", who,
+         (long long)prows);
+  joink_cols kc = {};
+  if (int rc = joink_check_cols(who, probe_keys, nkeys, &kc)) return rc;
+  if (ncond_cols < 1 || ncond_cols > GPUQ_PRED_MAX_COLS)
+    FAIL(GPUQ_ERR_INVALID, "%s: %d condition columns, need 1..%d", who, ncond_cols,
+         GPUQ_PRED_MAX_COLS);
+  if (!cond_cols) FAIL(GPUQ_ERR_INVALID, "%s: condition columns missing", who);
+  if (!cond_sides) FAIL(GPUQ_ERR_INVALID, "%s: condition sides missing", who);
+  if (!prog) FAIL(GPUQ_ERR_INVALID, "%s: condition program missing", who);
+  for (int c = 0; c < ncond_cols; c++)
+    if (cond_sides[c] != GPUQ_JOIN_SIDE_PROBE && cond_sides[c] != GPUQ_JOIN_SIDE_BUILD)
+      FAIL(GPUQ_ERR_INVALID, "%s: condition column %d has side %d, need 0 (probe) "
+           "or 1 (build)", who, c, cond_sides[c]);
+  if (ninsns < 1 || ninsns > GPUQ_PRED_MAX_INSNS)
+    FAIL(GPUQ_ERR_INVALID, "%s: %d instructions, need 1..%d", who, ninsns,
+         GPUQ_PRED_MAX_INSNS);
+  if (int rc = pred_check_program(who, cond_cols, ncond_cols, prog, ninsns)) return rc;
+  joinc_args a;
+  memset(&a, 0, sizeof(a));
+  for (int c = 0; c < ncond_cols; c++) {
+    a.data[c] = cond_cols[c].data;
+    a.validity[c] = cond_cols[c].validity;
+    a.dtype[c] = cond_cols[c].dtype;
+    a.side[c] = cond_sides[c];
+  }
+  for (int pc = 0; pc < ninsns; pc++) a.insn[pc] = prog[pc];
+  a.ncols = ncond_cols;
+  a.ninsns = ninsns;
+  joink_ws w; int64_t need;
+  joink_ws_layout(cap, brows, nkeys, &w, (char*)workspace, &need);
+  HIP_TRY(hipMemsetAsync(&w.sp->j.cursor, 0, 8, s));
+  if (prows > 0) {
+    int sw = joink_stride_words(nkeys);
+    dim3 jg((uint32_t)((prows + JOINC_CHUNK - 1) / JOINC_CHUNK));
+    hipEvent_t _pe = prof_begin(s);
+#define JKPC(JT) k_joink_probe_cond<JT><<<jg, 256, 0, s>>>( \
+        prows, kc, nkeys, sw, w.slots, w.next, w.sp, cap - 1, a, out_p, out_b, \
+        out_cap, w.matched)
+    switch (join_type) {
+      case 1: JKPC(1); break;
+      case 2: JKPC(2); break;
+      case 3: JKPC(3); break;
+      case 4: JKPC(4); break;
+      default: JKPC(0); break;
+    }
+#undef JKPC
+    prof_end("join_keys_probe_cond", s, _pe);
+    HIP_TRY(hipGetLastError());
+  }
+  joink_sp hsp;
+  HIP_TRY(hipMemcpyAsync(&hsp, w.sp, sizeof(hsp), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *out_nmatches = (int64_t)hsp.j.cursor;
+  if ((int64_t)hsp.j.cursor > out_cap)
+    FAIL(GPUQ_ERR_OVERFLOW, "%s: %lld matches exceed out_cap %lld", who,
+         (long long)hsp.j.cursor, (long long)out_cap);
   return GPUQ_OK;
 }
 

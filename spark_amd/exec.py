@@ -20,7 +20,7 @@ import torch
 
 from . import expression
 from .predicate import (And, Between, Cmp, Col, In, IsNotNull,  # noqa: F401
-                        IsNull, Not, Or, Pred)
+                        IsNull, Not, Or, Pred, columns_of)
 
 
 class ColumnarBatch:
@@ -251,6 +251,28 @@ def _join_key_tuples(left_key, right_key):
     return lk, rk
 
 
+def _check_join_condition(condition, left, right, null_aware_anti=False):
+    """The residual join condition of a hash / sort-merge join node
+    (HashJoin.scala boundCondition; SortMergeJoinExec.condition): None, or a
+    Pred each of whose columns is on exactly one side."""
+    if condition is None:
+        return None
+    if not isinstance(condition, Pred):
+        raise ValueError(f"join condition {condition!r} is not a predicate")
+    if null_aware_anti:
+        # BroadcastHashJoinExec.scala: isNullAwareAntiJoin requires
+        # condition.isEmpty
+        raise ValueError("the null-aware anti join takes no condition")
+    lo, ro = left.output, right.output
+    for name in columns_of(condition):
+        if name in lo and name in ro:
+            raise ValueError(f"join condition column {name!r} is ambiguous: "
+                             f"both sides have it")
+        if name not in lo and name not in ro:
+            raise ValueError(f"join condition reads unknown column {name!r}")
+    return condition
+
+
 class _JoinKeys:
     """left_key / right_key keep whatever the constructor was given (a name
     or a sequence); left_keys / right_keys are always tuples."""
@@ -269,14 +291,16 @@ class ShuffledHashJoinExec(_JoinKeys, _CpuNode):
     "left_anti" (ShuffledHashJoinExec.scala joinType; the preserved side
     must stream, so left-preserving types build on the right and
     vice versa). left_key / right_key: a column name, or 1-4 names per side
-    for a composite equi-join."""
+    for a composite equi-join. condition: the non-equi remainder of the ON
+    clause (a predicate over columns of both children), or None."""
 
     def __init__(self, left_key, right_key, build_side: str,
-                 left, right, join_type: str = "inner"):
+                 left, right, join_type: str = "inner", condition=None):
         super().__init__(left, right)
         _join_key_tuples(left_key, right_key)
         self.left_key, self.right_key, self.build_side = left_key, right_key, build_side
         self.join_type = join_type
+        self.condition = _check_join_condition(condition, left, right)
 
     @property
     def output(self):
@@ -293,11 +317,12 @@ class SortMergeJoinExec(_JoinKeys, _CpuNode):
     co-partitioned batches."""
 
     def __init__(self, left_key, right_key, left, right,
-                 join_type: str = "inner"):
+                 join_type: str = "inner", condition=None):
         super().__init__(left, right)
         _join_key_tuples(left_key, right_key)
         self.left_key, self.right_key = left_key, right_key
         self.join_type = join_type
+        self.condition = _check_join_condition(condition, left, right)
 
     @property
     def output(self):
@@ -482,12 +507,13 @@ class BroadcastHashJoinExec(_JoinKeys, _CpuNode):
     otherwise."""
 
     def __init__(self, left_key, right_key, build_side: str,
-                 left, right, join_type: str = "inner"):
+                 left, right, join_type: str = "inner", condition=None):
         super().__init__(left, right)
         assert build_side in ("left", "right")
         _join_key_tuples(left_key, right_key)
         self.left_key, self.right_key, self.build_side = left_key, right_key, build_side
         self.join_type = join_type
+        self.condition = _check_join_condition(condition, left, right)
 
     @property
     def output(self):
@@ -1391,12 +1417,18 @@ class GpuShuffledHashJoinExec(_JoinKeys, SparkPlan):
     clustered on the join key (ShuffledJoin.scala:57-69) — i.e. fed by (our)
     exchanges, as EnsureRequirements would arrange. One key column runs the
     single-key (LongHashedRelation-style) kernels; 2-4 key columns run the
-    composite-key table (gpuq_join_*_keys)."""
+    composite-key table (gpuq_join_*_keys). condition: the residual join
+    condition (HashJoin.scala boundCondition), a predicate over columns of
+    both children that a key-equal pair must make TRUE to count as a match;
+    with one, any key count runs the composite-key table and the probe
+    evaluates the condition itself (gpuq_join_probe_keys_cond)."""
 
     def __init__(self, left_key, right_key, build_side: str,
                  left, right, join_type: str = "inner",
-                 null_aware_anti: bool = False):
+                 null_aware_anti: bool = False, condition=None):
         super().__init__(left, right)
+        self.condition = _check_join_condition(condition, left, right,
+                                               null_aware_anti)
         assert build_side in ("left", "right")
         assert join_type in ("inner", "left_outer", "right_outer",
                              "left_semi", "left_anti", "full_outer")
@@ -1469,10 +1501,11 @@ class GpuShuffledHashJoinExec(_JoinKeys, SparkPlan):
         return ColumnarBatch(cols, validity=validity or None)
 
     def _execute_composite(self, gpuq, build, bkeys, pkeys, jt, probe_iter):
-        """2-4 key columns: one composite-key table over the concatenated
-        build side, probed batch-at-a-time. Full outer emits the unmatched
-        build rows ONCE, after the last probe batch, from the matched bits
-        the probes accumulated."""
+        """2-4 key columns, or any key count with a residual condition: one
+        composite-key table over the concatenated build side, probed
+        batch-at-a-time (the condition, if any, evaluated by the probe).
+        Full outer emits the unmatched build rows ONCE, after the last probe
+        batch, from the matched bits the probes accumulated."""
         bn = build.num_rows()
         nkeys = len(bkeys)
         cap = 1 << max(4, int(bn * 2 - 1).bit_length() if bn else 4)
@@ -1481,21 +1514,32 @@ class GpuShuffledHashJoinExec(_JoinKeys, SparkPlan):
             key_validities=[build.validity(k) for k in bkeys])
         full = self.join_type == "full_outer"
         probe_dtypes = None
+        bcols = build.columns()
+        bvalid = {n_: build.validity(n_) for n_ in bcols}
         for probe in probe_iter:
             pk = [probe.column(k) for k in pkeys]
             pkv = [probe.validity(k) for k in pkeys]
+            pcols = probe.columns()
+            pvalid = {n_: probe.validity(n_) for n_ in pcols}
+            if self.condition is not None:
+                cond = gpuq.lower_join_cond(self.condition, pcols, bcols)
             out_cap = max(int(probe.num_rows() * 2) + 64, 64)
             while True:
-                op, ob, nm = gpuq.join_probe_keys(pk, ws, cap, bn, out_cap,
-                                                  key_validities=pkv,
-                                                  join_type=jt)
+                if self.condition is None:
+                    op, ob, nm = gpuq.join_probe_keys(
+                        pk, ws, cap, bn, out_cap, key_validities=pkv,
+                        join_type=jt)
+                else:
+                    op, ob, nm = gpuq.join_probe_keys_cond(
+                        pk, ws, cap, bn, out_cap, cond, pcols, bcols,
+                        probe_validities=pvalid, build_validities=bvalid,
+                        key_validities=pkv, join_type=jt)
                 if op is not None:
                     break
                 out_cap = nm + 64
-            pcols = probe.columns()
             probe_dtypes = {n_: t.dtype for n_, t in pcols.items()}
             out = self._join_output(
-                build, pcols, {n_: probe.validity(n_) for n_ in pcols}, op, ob)
+                build, pcols, pvalid, op, ob)
             probe.close()
             yield out
         if full:
@@ -1524,7 +1568,7 @@ class GpuShuffledHashJoinExec(_JoinKeys, SparkPlan):
               "full_outer": gpuq.JOIN_FULL}[self.join_type]
         bkeys = self.left_keys if self.build_side == "left" else self.right_keys
         pkeys = self.right_keys if self.build_side == "left" else self.left_keys
-        if len(bkeys) > 1:
+        if len(bkeys) > 1 or self.condition is not None:
             yield from self._execute_composite(
                 gpuq, build, bkeys, pkeys, jt,
                 self.children[1 - bi].execute_columnar())
@@ -1876,7 +1920,8 @@ class GpuColumnarRule:
         if isinstance(plan, ShuffledHashJoinExec):
             return GpuShuffledHashJoinExec(plan.left_key, plan.right_key,
                                            plan.build_side, *children,
-                                           join_type=plan.join_type)
+                                           join_type=plan.join_type,
+                                           condition=plan.condition)
         if isinstance(plan, SortMergeJoinExec):
             # SMJ -> GPU hash join (same slot, same required distribution;
             # build on the right side as SHJ's default would choose). SMJ
@@ -1887,7 +1932,8 @@ class GpuColumnarRule:
             build = "left" if plan.join_type == "right_outer" else "right"
             j = GpuShuffledHashJoinExec(plan.left_key, plan.right_key,
                                         build, *children,
-                                        join_type=plan.join_type)
+                                        join_type=plan.join_type,
+                                        condition=plan.condition)
             declared = plan.output_ordering
             if self.preserve_smj_ordering and declared:
                 return GpuSortExec(declared, False, j)
@@ -1912,7 +1958,8 @@ class GpuColumnarRule:
         if isinstance(plan, BroadcastHashJoinExec):
             return GpuBroadcastHashJoinExec(plan.left_key, plan.right_key,
                                             plan.build_side, *children,
-                                            join_type=plan.join_type)
+                                            join_type=plan.join_type,
+                                            condition=plan.condition)
         plan.children = children
         return plan
 

@@ -170,6 +170,11 @@ def lib() -> ctypes.CDLL:
         L.gpuq_join_probe_keys.argtypes = [vp, i64, ctypes.POINTER(_Col), i32,
                                            vp, i64, i64, i32, vp, vp, i64,
                                            ctypes.POINTER(i64)]
+        L.gpuq_join_probe_keys_cond.restype = i32
+        L.gpuq_join_probe_keys_cond.argtypes = [
+            vp, i64, ctypes.POINTER(_Col), i32, vp, i64, i64, i32,
+            ctypes.POINTER(_Col), ctypes.POINTER(i32), i32,
+            ctypes.POINTER(_PredInsn), i32, vp, vp, i64, ctypes.POINTER(i64)]
         L.gpuq_join_keys_unmatched_build.restype = i32
         L.gpuq_join_keys_unmatched_build.argtypes = [vp, vp, i64, i64, i32,
                                                      vp, vp, i64,
@@ -529,6 +534,81 @@ def join_probe_keys(key_cols, workspace: torch.Tensor, capacity: int,
                                     workspace.data_ptr(), capacity, build_rows,
                                     join_type, op.data_ptr(), ob.data_ptr(),
                                     out_cap, ctypes.byref(nm))
+    if rc == 3:  # GPUQ_ERR_OVERFLOW: caller retries with nm.value capacity
+        return None, None, nm.value
+    _check(rc)
+    return op[:nm.value], ob[:nm.value], nm.value
+
+
+JOIN_SIDE_PROBE, JOIN_SIDE_BUILD = 0, 1
+
+
+def lower_join_cond(cond, probe_columns: dict, build_columns: dict):
+    """-> (names, sides, program): a residual join condition lowered by
+    predicate.lower over the merged schema of the two sides, and for each
+    column it reads the side it comes from. A column that both sides carry
+    raises ValueError (ambiguous), one that neither carries too (unknown)."""
+    for name in predicate.columns_of(cond):
+        if name in probe_columns and name in build_columns:
+            raise ValueError(f"join condition column {name!r} is ambiguous: "
+                             f"both sides have it")
+        if name not in probe_columns and name not in build_columns:
+            raise ValueError(f"join condition reads unknown column {name!r}")
+    schema = {k: t.dtype for k, t in build_columns.items()}
+    schema.update({k: t.dtype for k, t in probe_columns.items()})
+    names, prog = predicate.lower(cond, schema)
+    sides = [JOIN_SIDE_PROBE if k in probe_columns else JOIN_SIDE_BUILD
+             for k in names]
+    return names, sides, prog
+
+
+def join_probe_keys_cond(key_cols, workspace: torch.Tensor, capacity: int,
+                         build_rows: int, out_cap: int, cond,
+                         probe_columns: dict, build_columns: dict,
+                         probe_validities: dict = None,
+                         build_validities: dict = None, key_validities=None,
+                         join_type: int = JOIN_INNER):
+    """join_probe_keys with a residual join condition evaluated inside the
+    probe: a key-equal (probe row, build row) pair counts as a match only if
+    cond is TRUE for it (FALSE and NULL fail), which is what decides outer
+    fills, semi / anti membership and full outer's matched bits.
+
+    cond is a predicate.Pred over the columns of probe_columns (name ->
+    tensor, one row per probe row) and build_columns (one row per build row
+    of the table), or an already lowered (names, sides, program) triple from
+    lower_join_cond. Returns (op, ob, n), or (None, None, n) on output
+    overflow, like join_probe_keys."""
+    probe_validities = probe_validities or {}
+    build_validities = build_validities or {}
+    if isinstance(cond, predicate.Pred):
+        names, sides, prog = lower_join_cond(cond, probe_columns, build_columns)
+    else:
+        names, sides, prog = cond
+    nkeys = len(key_cols)
+    pn = key_cols[0].numel()
+    dev = key_cols[0].device
+    cols = []
+    for name, side in zip(names, sides):
+        src, val, rows = ((probe_columns, probe_validities, pn)
+                          if side == JOIN_SIDE_PROBE
+                          else (build_columns, build_validities, build_rows))
+        if src[name].numel() != rows:
+            raise ValueError(f"join_probe_keys_cond: column {name!r} has "
+                             f"{src[name].numel()} rows, expected {rows}")
+        cols.append(_col(src[name], val.get(name)))
+    keys_arr = _key_cols_arr(key_cols, key_validities)
+    cols_arr = (_Col * max(len(cols), 1))(*cols)
+    sides_arr = (ctypes.c_int32 * max(len(sides), 1))(*sides)
+    prog_arr = (_PredInsn * max(len(prog), 1))(
+        *[_PredInsn(*insn) for insn in prog])
+    op = torch.empty(out_cap, dtype=torch.int32, device=dev)
+    ob = torch.empty(out_cap, dtype=torch.int32, device=dev)
+    nm = ctypes.c_int64(0)
+    rc = lib().gpuq_join_probe_keys_cond(
+        _stream(), pn, keys_arr, nkeys, workspace.data_ptr(), capacity,
+        build_rows, join_type, cols_arr, sides_arr, len(cols),
+        prog_arr, len(prog), op.data_ptr(), ob.data_ptr(), out_cap,
+        ctypes.byref(nm))
     if rc == 3:  # GPUQ_ERR_OVERFLOW: caller retries with nm.value capacity
         return None, None, nm.value
     _check(rc)

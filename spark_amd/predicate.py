@@ -297,6 +297,37 @@ class _Lowering:
             raise ValueError(f"not a predicate: {p!r}")
 
 
+def columns_of(pred):
+    """-> the column names pred references, each once, in order of first use.
+    Needs no schema: a join node uses it to tell which side each column of its
+    residual condition comes from. The walk is lower()'s (the operands of an
+    And / Or regrouped by column), so for a predicate that lowers the result
+    is lower()'s column list."""
+    names = []
+
+    def use(name):
+        if name not in names:
+            names.append(name)
+
+    def walk(p):
+        if isinstance(p, Cmp):
+            use(p.col)
+            if isinstance(p.rhs, Col):
+                use(p.rhs.name)
+        elif isinstance(p, (IsNull, IsNotNull, In, Between)):
+            use(p.col)
+        elif isinstance(p, (And, Or)):
+            for q in _group_by_col(p.ps):
+                walk(q)
+        elif isinstance(p, Not):
+            walk(p.p)
+        else:
+            raise ValueError(f"not a predicate: {p!r}")
+
+    walk(pred)
+    return names
+
+
 def stack_depth(program) -> int:
     """Largest evaluation-stack depth of a postfix program."""
     depth = peak = 0
