@@ -889,6 +889,66 @@ int gpuq_window_shift(void* stream, int64_t nrows, gpuq_col val, int64_t offset,
                       const uint64_t* part_start, void* out, uint8_t* out_validity_bits,
                       void* workspace, int64_t workspace_bytes);
 
+/* Sliding ROWS BETWEEN frames (WindowFunctionFrame.scala's
+ * SlidingWindowFunctionFrame and UnboundedPrecedingWindowFunctionFrame) and
+ * first_value / last_value. */
+#define GPUQ_WIN_FIRST_VALUE 7   /* gpuq_window_slide only */
+#define GPUQ_WIN_LAST_VALUE  8   /* gpuq_window_slide only */
+#define GPUQ_WIN_UNBOUNDED_PRECEDING INT64_MIN
+#define GPUQ_WIN_UNBOUNDED_FOLLOWING INT64_MAX
+#define GPUQ_WIN_SLIDE_MAX_SPAN 2048   /* hi - lo of a two-sided bounded frame */
+
+/* workspace bytes for gpuq_window_slide at (nrows, lo, hi): the scan's
+ * workspace, plus nrows 8-byte words and a bitmap when lo is unbounded. Pure
+ * arithmetic; 0 for arguments gpuq_window_slide would refuse. */
+int64_t gpuq_window_slide_workspace_bytes(int64_t nrows, int64_t lo, int64_t hi);
+
+/* out[i] = op over the frame ROWS BETWEEN lo AND hi of row i, given the
+ * partition bitmap gpuq_window_boundaries produced for the same rows.
+ * Frame: row i lies in the partition [pb, pe] (inclusive row positions); its
+ * frame is the rows first..last with first = max(pb, i + lo) and last =
+ * min(pe, i + hi), and it is EMPTY when first > last. lo ==
+ * GPUQ_WIN_UNBOUNDED_PRECEDING means first = pb, hi ==
+ * GPUQ_WIN_UNBOUNDED_FOLLOWING means last = pe. Finite offsets are signed row
+ * counts (negative PRECEDING, 0 CURRENT ROW, positive FOLLOWING) that fit
+ * int32, with lo <= hi.
+ * Accepted shapes: (a) both finite with hi - lo <= GPUQ_WIN_SLIDE_MAX_SPAN,
+ * at any distance from the row (5000 FOLLOWING .. 5002 FOLLOWING is legal);
+ * (b) lo unbounded with hi finite or unbounded. A finite lo with an unbounded
+ * hi is refused (it needs a backward scan).
+ * Ops: COUNT (val.data == NULL: COUNT(*)), SUM, MIN, MAX, FIRST_VALUE,
+ * LAST_VALUE; out is nrows 8-byte values typed as gpuq_window_scan's, and as
+ * val for FIRST / LAST.
+ * Results follow gpuq_window_scan's NULL / NaN rules: SUM / MIN / MAX skip
+ * NULL rows; a row's result is NULL iff its frame holds no non-NULL value (an
+ * empty frame is such a frame); NULL rows hold 0; COUNT is never NULL and is
+ * 0 for an empty frame; int64 SUM wraps; float64 MIN / MAX order by the
+ * sort-key encoding and return the canonical NaN and +0.0. FIRST_VALUE /
+ * LAST_VALUE (ignoreNulls = false) copy the value and NULL-ness of row first
+ * / last and give NULL for an empty frame.
+ * float64 SUM, shape (a): acc = +0.0, then acc += v for the non-NULL rows
+ * first..last in ascending row order, plain IEEE adds: the result equals that
+ * expression bit for bit (any NaN counts as NaN). No prefix differences are
+ * taken, so nothing cancels, inf - inf does not arise and a NaN reaches only
+ * the frames that hold it. Shape (b) runs gpuq_window_scan's ROWS scan and
+ * inherits its tile-order sum and reordering error.
+ * out_validity_bits ((nrows + 7) / 8 bytes) is required for FIRST / LAST, and
+ * for SUM / MIN / MAX when the column has a bitmap or the frame can be empty
+ * (lo > 0 or hi < 0). It is optional for COUNT; when given it comes out all
+ * valid.
+ * val (and its bitmap) and part_start are read on the stream and never
+ * written; out must not overlap them or the workspace.
+ * GPUQ_ERR_INVALID before anything is launched: nrows < 0 or > 0xFFFFFFFF; a
+ * bad op; a dtype other than int64 / float64; val.data == NULL for any op but
+ * COUNT (and nrows > 0); lo > hi; a finite offset outside int32; a span over
+ * the cap; a finite lo with an unbounded hi; a missing required
+ * out_validity_bits (and nrows > 0); a short workspace. nrows == 0 returns
+ * GPUQ_OK with nothing launched. */
+int gpuq_window_slide(void* stream, int64_t nrows, int32_t op, gpuq_col val,
+                      int64_t lo, int64_t hi, const uint64_t* part_start,
+                      void* out, uint8_t* out_validity_bits,
+                      void* workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7207,6 +7207,200 @@ void k_win_shift(int64_t n, const wu64* d, const uint8_t* v, int64_t offset,
   }
 }
 
+/* ---- sliding ROWS frames (SlidingWindowFunctionFrame) ----
+ * Row i of the partition [pb, pe] aggregates the rows first..last, first =
+ * max(pb, i + lo), last = min(pe, i + hi); the frame is empty when first >
+ * last. Spark re-adds the frame's rows in row order for every output row, and
+ * so does k_win_slide: a difference of prefix sums would cancel, turn inf -
+ * inf into NaN and let one NaN poison the rest of its partition.
+ *
+ * One block per WIN_TILE rows in the row layout of the scans. The block
+ * stages the rows [tile_base + lo, tile_base + WIN_TILE - 1 + hi] that lie in
+ * [0, nrows) once into LDS, element e = row - (tile_base + lo): s_val[e] is
+ * the raw word (SUM, FIRST / LAST) or the encode_* word (MIN / MAX), and the
+ * operator's identity for a NULL row or a row outside the input, so the loop
+ * of a row folds s_val[first..last] without looking at validity (a float64
+ * accumulator that starts at +0.0 never becomes -0.0, so adding the +0.0 of a
+ * NULL row changes no bit). Validity is staged as one ballot word per 64
+ * elements plus the exclusive prefix of their popcounts: the non-NULL count
+ * of first..last is two rank lookups, and it alone decides NULL-ness. COUNT
+ * and FIRST / LAST need no loop. The 64 lanes of a wave own consecutive rows
+ * and their loops start at consecutive elements (clipped lanes of one
+ * partition share an address): 8-byte reads of one bank row per half wave.
+ * LDS: (WIN_TILE + WIN_SLIDE_MAX_SPAN) * 8 bytes = 32 KiB of values and
+ * about 1 KiB of validity words, counts, partition words and tables. */
+#define WIN_SLIDE_MAX_SPAN GPUQ_WIN_SLIDE_MAX_SPAN
+#define WIN_STAGE (WIN_TILE + WIN_SLIDE_MAX_SPAN)
+#define WIN_STAGE_WORDS (WIN_STAGE / WAVE)
+
+#define SK_COUNT 0
+#define SK_SUM_U64 1
+#define SK_SUM_F64 2
+#define SK_MIN 3
+#define SK_MAX 4
+#define SK_FIRST 5
+#define SK_LAST 6
+
+/* non-NULL staged elements before element q, q <= WIN_STAGE */
+DEV uint32_t win_stage_rank(const wu64* vw, const uint32_t* vc, int q) {
+  return vc[q >> 6] + (uint32_t)__popcll(vw[q >> 6] & ((1ULL << (q & 63)) - 1));
+}
+
+template <int KIND>
+__global__ __launch_bounds__(WIN_BLOCK)
+void k_win_slide(int64_t n, int f64, const wu64* d, const uint8_t* v,
+                 int64_t lo, int64_t hi, const wu64* part,
+                 const uint32_t* prev_part, const uint32_t* next_part,
+                 wu64* out, uint8_t* out_valid, int64_t nbytes) {
+  __shared__ wu64 s_val[KIND == SK_COUNT ? 1 : WIN_STAGE];
+  __shared__ wu64 s_vw[WIN_STAGE_WORDS + 1];
+  __shared__ uint32_t s_vc[WIN_STAGE_WORDS + 1];
+  __shared__ uint32_t s_pb[WIN_WORDS], s_pe[WIN_WORDS];
+  __shared__ wu64 s_pw[WIN_WORDS];                     /* the tile's partition words */
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  const int64_t tile = blockIdx.x;
+  const int64_t nwords = (n + WAVE - 1) / WAVE;
+  const int64_t sbase = tile * WIN_TILE + lo;          /* row of element 0 */
+  const int ne = WIN_TILE + (int)(hi - lo);            /* staged elements */
+  const int rounds = (ne + WIN_BLOCK - 1) / WIN_BLOCK; /* <= 16 */
+  const wu64 ident = KIND == SK_MIN ? ~0ULL : 0ULL;
+  if (wave == 0) win_begin_table(part, nwords, tile, prev_part[tile], s_pb, lane);
+  if (wave == 1) win_end_table(part, nwords, tile, next_part[tile], s_pe, lane);
+  if (wave == 2 && lane < WIN_WORDS) {
+    const int64_t gw = tile * WIN_WORDS + lane;
+    s_pw[lane] = gw < nwords ? part[gw] : 0;
+  }
+  for (int k = 0; k < rounds; k++) {
+    const int e = k * WIN_BLOCK + threadIdx.x;
+    const int64_t row = sbase + e;
+    const bool ok = e < ne && row >= 0 && row < n && (!d || bit_valid(v, row));
+    if (KIND != SK_COUNT) {
+      wu64 x = ident;
+      if (ok) {
+        x = d[row];
+        if (KIND == SK_MIN || KIND == SK_MAX)
+          x = f64 ? encode_f64(__longlong_as_double((long long)x))
+                  : encode_i64((int64_t)x);
+      }
+      s_val[e] = x;
+    }
+    const wu64 m = __ballot(ok);
+    if (lane == 0) s_vw[k * WIN_WAVES + wave] = m;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    /* words past the staged rounds read as empty; s_vc[w] = non-NULL
+     * elements in the words before w */
+    const wu64 m = lane < rounds * WIN_WAVES ? s_vw[lane] : 0;
+    uint32_t c = (uint32_t)__popcll(m);
+    #pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+      uint32_t y = __shfl_up(c, off);
+      if (lane >= off) c += y;
+    }
+    s_vw[lane] = m;
+    s_vc[lane + 1] = c;
+    if (lane == 0) { s_vc[0] = 0; s_vw[WIN_STAGE_WORDS] = 0; }
+  }
+  __syncthreads();
+  #pragma unroll 2
+  for (int r = 0; r < WIN_ITEMS; r++) {
+    const int wd = r * WIN_WAVES + wave;
+    const int64_t gw = tile * WIN_WORDS + wd;
+    const int64_t i = gw * WAVE + lane;
+    bool valid = false;
+    if (i < n) {
+      const wu64 m = s_pw[wd];
+      const int64_t pb = win_begin_of(m, lane, gw * WAVE, s_pb[wd]);
+      const int64_t pe = win_end_of(m, lane, gw * WAVE, s_pe[wd], n);
+      const int64_t first = i + lo > pb ? i + lo : pb;
+      const int64_t last = i + hi < pe ? i + hi : pe;
+      wu64 o = 0;
+      valid = KIND == SK_COUNT;
+      if (first <= last) {
+        /* 0 <= a <= b < ne: first >= tile_base + lo, last <= i + hi */
+        const int a = (int)(first - sbase), b = (int)(last - sbase);
+        if (KIND == SK_FIRST || KIND == SK_LAST) {
+          const int p = KIND == SK_FIRST ? a : b;
+          valid = (s_vw[p >> 6] >> (p & 63)) & 1;
+          o = s_val[p];
+        } else {
+          const uint32_t cnt = win_stage_rank(s_vw, s_vc, b + 1) -
+                               win_stage_rank(s_vw, s_vc, a);
+          if (KIND == SK_COUNT) {
+            o = cnt;
+          } else if (cnt > 0) {
+            valid = true;
+            if (KIND == SK_SUM_F64) {
+              double acc = 0.0;
+              #pragma unroll 4
+              for (int p = a; p <= b; p++)
+                acc += __longlong_as_double((long long)s_val[p]);
+              o = (wu64)__double_as_longlong(acc);
+            } else {
+              wu64 acc = ident;
+              #pragma unroll 4
+              for (int p = a; p <= b; p++) {
+                const wu64 x = s_val[p];
+                acc = KIND == SK_MIN ? (x < acc ? x : acc)
+                    : KIND == SK_MAX ? (x > acc ? x : acc) : acc + x;
+              }
+              o = KIND == SK_SUM_U64 ? acc
+                : f64 ? (wu64)__double_as_longlong(decode_f64(acc))
+                      : (wu64)decode_i64(acc);
+            }
+          }
+        }
+      }
+      out[i] = o;
+    }
+    win_store_valid(out_valid, nbytes, gw, __ballot(valid), lane);
+  }
+}
+
+/* Frames that start at UNBOUNDED PRECEDING and end hi rows from the row (hi
+ * already clamped to [-nrows, nrows]; nrows stands for UNBOUNDED FOLLOWING):
+ * the frame of row i is the ROWS-scan frame of row j = min(i + hi, pe), and
+ * it is empty when i + hi < pb. mode 0: out[i] = src[j] with src's validity
+ * (the scan's result in the workspace); 1: FIRST_VALUE, src[pb]; 2:
+ * LAST_VALUE, src[j] (src the value column). An empty frame gives 0, NULL
+ * unless never_null. NULL rows hold 0. */
+__global__ __launch_bounds__(WIN_BLOCK)
+void k_win_pick(int64_t n, int mode, int64_t hi, const wu64* src,
+                const uint8_t* src_valid, int never_null, const wu64* part,
+                const uint32_t* prev_part, const uint32_t* next_part,
+                wu64* out, uint8_t* out_valid, int64_t nbytes) {
+  __shared__ uint32_t s_pb[WIN_WORDS], s_pe[WIN_WORDS];
+  const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+  const int64_t tile = blockIdx.x;
+  const int64_t nwords = (n + WAVE - 1) / WAVE;
+  if (wave == 0) win_begin_table(part, nwords, tile, prev_part[tile], s_pb, lane);
+  if (wave == 1) win_end_table(part, nwords, tile, next_part[tile], s_pe, lane);
+  __syncthreads();
+  #pragma unroll
+  for (int r = 0; r < WIN_ITEMS; r++) {
+    const int wd = r * WIN_WAVES + wave;
+    const int64_t gw = tile * WIN_WORDS + wd;
+    const int64_t i = gw * WAVE + lane;
+    bool valid = false;
+    if (i < n) {
+      const wu64 m = part[gw];
+      const int64_t pb = win_begin_of(m, lane, gw * WAVE, s_pb[wd]);
+      const int64_t pe = win_end_of(m, lane, gw * WAVE, s_pe[wd], n);
+      const int64_t j = i + hi < pe ? i + hi : pe;
+      wu64 o = 0;
+      valid = never_null != 0;
+      if (j >= pb) {
+        const int64_t p = mode == 1 ? pb : j;
+        valid = never_null || bit_valid(src_valid, p);
+        if (valid) o = src[p];
+      }
+      out[i] = o;
+    }
+    win_store_valid(out_valid, nbytes, gw, __ballot(valid), lane);
+  }
+}
+
 extern "C" int gpuq_window_boundaries(void* stream, int64_t n, const gpuq_col* keys,
                                       int32_t nkeys, int32_t npart,
                                       uint64_t* out_part_start,
@@ -7378,6 +7572,170 @@ extern "C" int gpuq_window_shift(void* stream, int64_t n, gpuq_col val, int64_t 
       (const wu64*)part_start, w.prev_part, w.next_part, (wu64*)out,
       out_validity_bits, (n + 7) / 8);
   prof_end("win_shift", s, _pe); }
+  HIP_TRY(hipGetLastError());
+  return GPUQ_OK;
+}
+
+/* ---- sliding frames: host side ---- */
+
+/* NULL when (lo, hi) is a frame gpuq_window_slide runs, else what is wrong */
+static const char* win_slide_frame_error(int64_t lo, int64_t hi) {
+  const bool lo_unb = lo == GPUQ_WIN_UNBOUNDED_PRECEDING;
+  const bool hi_unb = hi == GPUQ_WIN_UNBOUNDED_FOLLOWING;
+  if (!lo_unb && (lo < INT32_MIN || lo > INT32_MAX)) return "lo does not fit int32";
+  if (!hi_unb && (hi < INT32_MIN || hi > INT32_MAX)) return "hi does not fit int32";
+  if (!lo_unb && hi_unb)
+    return "a finite lo with UNBOUNDED FOLLOWING is not supported";
+  if (!lo_unb && lo > hi) return "lo > hi";
+  if (!lo_unb && hi - lo > GPUQ_WIN_SLIDE_MAX_SPAN) return "span hi - lo over the cap";
+  return nullptr;
+}
+
+/* the scan's workspace first; frames from UNBOUNDED PRECEDING add the scan's
+ * result: nrows words and a bitmap */
+static void win_slide_ws_layout(int64_t n, int64_t lo, win_ws* w, char* basep,
+                                wu64** tmp, uint8_t** tmp_valid, int64_t* total) {
+  int64_t off;
+  win_ws_layout(n, w, basep, &off);
+  *tmp = nullptr; *tmp_valid = nullptr;
+  if (lo == GPUQ_WIN_UNBOUNDED_PRECEDING) {
+    *tmp = (wu64*)(basep ? basep + off : nullptr);
+    off += (n * 8 + 255) & ~255LL;
+    *tmp_valid = (uint8_t*)(basep ? basep + off : nullptr);
+    off += ((n + 7) / 8 + 255) & ~255LL;
+  }
+  *total = off;
+}
+
+extern "C" int64_t gpuq_window_slide_workspace_bytes(int64_t n, int64_t lo, int64_t hi) {
+  if (n < 0 || n > 0xFFFFFFFFLL || win_slide_frame_error(lo, hi)) return 0;
+  win_ws w; wu64* tmp; uint8_t* tv; int64_t total;
+  win_slide_ws_layout(n, lo, &w, nullptr, &tmp, &tv, &total);
+  return total;
+}
+
+template <int KIND>
+static void win_slide_launch(hipStream_t s, int64_t n, int f64, gpuq_col val,
+                             int64_t lo, int64_t hi, const uint64_t* part,
+                             win_ws& w, void* out, uint8_t* out_valid) {
+  const int64_t nt = (n + WIN_TILE - 1) / WIN_TILE;
+  hipEvent_t _pe = prof_begin(s);
+  k_win_slide<KIND><<<dim3((uint32_t)nt), WIN_BLOCK, 0, s>>>(
+      n, f64, (const wu64*)val.data, val.validity, lo, hi, (const wu64*)part,
+      w.prev_part, w.next_part, (wu64*)out, out_valid, (n + 7) / 8);
+  prof_end("win_slide", s, _pe);
+}
+
+extern "C" int gpuq_window_slide(void* stream, int64_t n, int32_t op, gpuq_col val,
+                                 int64_t lo, int64_t hi, const uint64_t* part_start,
+                                 void* out, uint8_t* out_validity_bits,
+                                 void* workspace, int64_t workspace_bytes) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 0 || n > 0xFFFFFFFFLL)
+    FAIL(GPUQ_ERR_INVALID, "window_slide: nrows %lld out of range", (long long)n);
+  if (op < GPUQ_WIN_COUNT || op > GPUQ_WIN_LAST_VALUE)
+    FAIL(GPUQ_ERR_INVALID, "window_slide: bad op %d", op);
+  const bool reads_val = op != GPUQ_WIN_COUNT || val.data;
+  if (reads_val && val.dtype != GPUQ_INT64 && val.dtype != GPUQ_FLOAT64)
+    FAIL(GPUQ_ERR_INVALID, "window_slide: unsupported dtype %d", val.dtype);
+  /* an empty column's pointer may be NULL */
+  if (n > 0 && op != GPUQ_WIN_COUNT && !val.data)
+    FAIL(GPUQ_ERR_INVALID, "window_slide: op %d needs a value column", op);
+  if (const char* why = win_slide_frame_error(lo, hi))
+    FAIL(GPUQ_ERR_INVALID, "window_slide: bad frame (%lld, %lld): %s",
+         (long long)lo, (long long)hi, why);
+  const bool lo_unb = lo == GPUQ_WIN_UNBOUNDED_PRECEDING;
+  const bool pick_val = op >= GPUQ_WIN_FIRST_VALUE;
+  const bool can_be_empty = (!lo_unb && lo > 0) || hi < 0;
+  /* an empty bitmap's pointer may be NULL too */
+  if (n > 0 && !out_validity_bits &&
+      (pick_val || (op != GPUQ_WIN_COUNT && (val.validity || can_be_empty))))
+    FAIL(GPUQ_ERR_INVALID, "window_slide: op %d over this column and frame "
+         "needs an output bitmap", op);
+  win_ws w; wu64* tmp; uint8_t* tmp_valid; int64_t need;
+  win_slide_ws_layout(n, lo, &w, (char*)workspace, &tmp, &tmp_valid, &need);
+  if (workspace_bytes < need)
+    FAIL(GPUQ_ERR_INVALID, "window_slide: workspace %lld < %lld",
+         (long long)workspace_bytes, (long long)need);
+  if (n == 0) return GPUQ_OK;
+  const int64_t nt = (n + WIN_TILE - 1) / WIN_TILE;
+  const int f64 = val.dtype == GPUQ_FLOAT64;
+  if (!reads_val) val.validity = nullptr;
+  if (!lo_unb) {
+    /* positions only; the partition bitmap stands in for the peer bitmap */
+    win_reduce_carry<WK_NONE>(s, n, WS_ONE, val, part_start, part_start, w);
+    switch (op) {
+      case GPUQ_WIN_COUNT:
+        win_slide_launch<SK_COUNT>(s, n, f64, val, lo, hi, part_start, w, out,
+                                   out_validity_bits);
+        break;
+      case GPUQ_WIN_SUM:
+        if (f64) win_slide_launch<SK_SUM_F64>(s, n, f64, val, lo, hi, part_start, w,
+                                              out, out_validity_bits);
+        else win_slide_launch<SK_SUM_U64>(s, n, f64, val, lo, hi, part_start, w, out,
+                                          out_validity_bits);
+        break;
+      case GPUQ_WIN_MIN:
+        win_slide_launch<SK_MIN>(s, n, f64, val, lo, hi, part_start, w, out,
+                                 out_validity_bits);
+        break;
+      case GPUQ_WIN_MAX:
+        win_slide_launch<SK_MAX>(s, n, f64, val, lo, hi, part_start, w, out,
+                                 out_validity_bits);
+        break;
+      case GPUQ_WIN_FIRST_VALUE:
+        win_slide_launch<SK_FIRST>(s, n, f64, val, lo, hi, part_start, w, out,
+                                   out_validity_bits);
+        break;
+      default:
+        win_slide_launch<SK_LAST>(s, n, f64, val, lo, hi, part_start, w, out,
+                                  out_validity_bits);
+        break;
+    }
+    HIP_TRY(hipGetLastError());
+    return GPUQ_OK;
+  }
+  /* UNBOUNDED PRECEDING .. hi: an offset past either end of the input is past
+   * every partition, and nrows rows ahead is UNBOUNDED FOLLOWING */
+  if (hi > n) hi = n;
+  if (hi < -n) hi = -n;
+  const wu64* src = (const wu64*)val.data;
+  const uint8_t* src_valid = val.validity;
+  int mode = 0, never_null = 0;
+  if (pick_val) {
+    mode = op == GPUQ_WIN_FIRST_VALUE ? 1 : 2;
+    win_reduce_carry<WK_NONE>(s, n, WS_ONE, val, part_start, part_start, w);
+  } else {
+    never_null = op == GPUQ_WIN_COUNT;
+    src = tmp;
+    src_valid = never_null ? nullptr : tmp_valid;
+    switch (op) {
+      case GPUQ_WIN_COUNT:
+        win_scan_rows<WK_ADD_U64>(s, n, val.data ? WS_VALID : WS_ONE, val, part_start,
+                                  part_start, w, 0, 1, tmp, nullptr);
+        break;
+      case GPUQ_WIN_SUM:
+        if (f64) win_scan_rows<WK_ADD_F64>(s, n, WS_RAW, val, part_start, part_start,
+                                           w, 0, 0, tmp, tmp_valid);
+        else win_scan_rows<WK_ADD_U64>(s, n, WS_RAW, val, part_start, part_start, w,
+                                       0, 0, tmp, tmp_valid);
+        break;
+      case GPUQ_WIN_MIN:
+        win_scan_rows<WK_MIN>(s, n, f64 ? WS_ENC_F64 : WS_ENC_I64, val, part_start,
+                              part_start, w, f64 ? 2 : 1, 0, tmp, tmp_valid);
+        break;
+      default:
+        win_scan_rows<WK_MAX>(s, n, f64 ? WS_ENC_F64 : WS_ENC_I64, val, part_start,
+                              part_start, w, f64 ? 2 : 1, 0, tmp, tmp_valid);
+        break;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  { hipEvent_t _pe = prof_begin(s);
+  k_win_pick<<<dim3((uint32_t)nt), WIN_BLOCK, 0, s>>>(
+      n, mode, hi, src, src_valid, never_null, (const wu64*)part_start,
+      w.prev_part, w.next_part, (wu64*)out, out_validity_bits, (n + 7) / 8);
+  prof_end("win_pick", s, _pe); }
   HIP_TRY(hipGetLastError());
   return GPUQ_OK;
 }

@@ -401,7 +401,19 @@ class ProjectExec(_CpuNode):
 WINDOW_RANK_FNS = ("row_number", "rank", "dense_rank")
 WINDOW_AGG_FNS = ("count", "sum", "min", "max", "avg")
 WINDOW_SHIFT_FNS = ("lag", "lead")
+WINDOW_VALUE_FNS = ("first_value", "last_value")
 WINDOW_FRAMES = ("rows", "range", "partition")
+
+
+@dataclass(frozen=True)
+class RowsBetween:
+    """ROWS BETWEEN lo AND hi: signed row offsets from the current row
+    (negative PRECEDING, 0 CURRENT ROW, positive FOLLOWING), None for
+    UNBOUNDED PRECEDING (lo) / UNBOUNDED FOLLOWING (hi). Row i of the
+    partition [pb, pe] sees the rows max(pb, i + lo) .. min(pe, i + hi); the
+    frame is empty when that range is."""
+    lo: Optional[int]
+    hi: Optional[int]
 
 
 @dataclass
@@ -413,13 +425,36 @@ class WindowExpr:
     UNBOUNDED PRECEDING AND CURRENT ROW), "range" (RANGE ... CURRENT ROW:
     peers share a value) or "partition" (the whole partition); None is
     Spark's default, "range" with an ORDER BY and "partition" without one.
-    offset / default are lag's and lead's (ignoreNulls = false)."""
+    A RowsBetween(lo, hi) is a sliding ROWS frame; it needs an ORDER BY, as
+    do first_value / last_value (ignoreNulls = false), which take any frame
+    an aggregate takes. offset / default are lag's and lead's (ignoreNulls =
+    false)."""
     fn: str
     col: Optional[str]
     name: str
-    frame: Optional[str] = None
+    frame: object = None
     offset: int = 1
     default: object = None
+
+
+def _rows_between_check(e, order_spec):
+    """a RowsBetween frame on expression e, as gpuq_window_slide takes it."""
+    f = e.frame
+    if e.fn in WINDOW_RANK_FNS + WINDOW_SHIFT_FNS:
+        raise ValueError(f"window: {e.fn} takes no frame, got {f!r}")
+    for b in (f.lo, f.hi):
+        if b is None:
+            continue
+        if isinstance(b, bool) or not isinstance(b, int):
+            raise ValueError(f"window: frame offset {b!r} is not an int")
+        if not -(1 << 31) <= b < (1 << 31):
+            raise ValueError(f"window: frame offset {b} does not fit int32")
+    if f.lo is not None and f.hi is None:
+        raise ValueError(f"window: {f!r} (k .. UNBOUNDED FOLLOWING) unsupported")
+    if f.lo is not None and f.lo > f.hi:
+        raise ValueError(f"window: {f!r} has lo > hi")
+    if not order_spec:
+        raise ValueError(f"window: a sliding frame {f!r} needs an ORDER BY")
 
 
 def _window_check(window_exprs, partition_spec, order_spec, child):
@@ -432,10 +467,15 @@ def _window_check(window_exprs, partition_spec, order_spec, child):
                   else list(order_spec))
     names = list(child.output)
     for e in window_exprs:
-        if e.fn not in WINDOW_RANK_FNS + WINDOW_AGG_FNS + WINDOW_SHIFT_FNS:
+        if e.fn not in (WINDOW_RANK_FNS + WINDOW_AGG_FNS + WINDOW_SHIFT_FNS
+                        + WINDOW_VALUE_FNS):
             raise ValueError(f"window: unknown function {e.fn!r}")
-        if e.frame is not None and e.frame not in WINDOW_FRAMES:
+        if isinstance(e.frame, RowsBetween):
+            _rows_between_check(e, order_spec)
+        elif e.frame is not None and e.frame not in WINDOW_FRAMES:
             raise ValueError(f"window: unknown frame {e.frame!r}")
+        if e.fn in WINDOW_VALUE_FNS and not order_spec:
+            raise ValueError(f"window: {e.fn} needs an ORDER BY")
         if e.fn in WINDOW_RANK_FNS and e.col is not None:
             raise ValueError(f"window: {e.fn} takes no column")
         if e.fn not in WINDOW_RANK_FNS and e.fn != "count" and e.col is None:
@@ -468,10 +508,10 @@ class _WindowSpec:
     def required_child_ordering(self):
         return [SortOrder(k) for k in self.partition_spec] + list(self.order_spec)
 
-    def frame_of(self, e: "WindowExpr") -> str:
+    def frame_of(self, e: "WindowExpr"):
         """the frame an aggregate runs under: Spark's default when none is
         given, and "range" without an ORDER BY is the whole partition (every
-        row is a peer of every other)."""
+        row is a peer of every other). A RowsBetween is returned as it is."""
         frame = e.frame or ("range" if self.order_spec else "partition")
         if frame == "range" and not self.order_spec:
             frame = "partition"
@@ -1775,7 +1815,9 @@ class GpuWindowExec(_WindowSpec, SparkPlan):
     and every expression is one segmented scan (gpuq_window_scan) or shift
     (gpuq_window_shift) under them. Yields one batch: every input column and
     bitmap untouched, plus one column per expression. avg (float64 only) is
-    windowed SUM / cast(windowed COUNT), NULL where the count is 0."""
+    windowed SUM / cast(windowed COUNT), NULL where the count is 0. A
+    RowsBetween frame other than (None, 0) / (None, None), and first_value /
+    last_value, run through gpuq_window_slide."""
 
     def __init__(self, window_exprs, partition_spec, order_spec, child):
         super().__init__(child)
@@ -1798,6 +1840,12 @@ class GpuWindowExec(_WindowSpec, SparkPlan):
             return gpuq.window_shift(val, off, part_bits, validity=valid,
                                      default=e.default, workspace=ws)
         frame = self.frame_of(e)
+        if e.fn in WINDOW_VALUE_FNS:
+            return self._eval_value(gpuq, e, frame, val, valid, part_bits)
+        if isinstance(frame, RowsBetween):
+            if frame.lo is not None or frame.hi not in (None, 0):
+                return self._eval_slide(gpuq, e, frame, val, valid, n, part_bits)
+            frame = "rows" if frame.hi == 0 else "partition"
         if e.fn != "avg":
             return gpuq.window_scan(e.fn, frame, part_bits, peer_bits, val=val,
                                     validity=valid, n=n, workspace=ws)
@@ -1808,6 +1856,39 @@ class GpuWindowExec(_WindowSpec, SparkPlan):
                                          val=val, validity=valid, workspace=ws)
         cnt, _ = gpuq.window_scan("count", frame, part_bits, peer_bits,
                                   val=val, validity=valid, workspace=ws)
+        # x / 0 is NULL: the rows whose frame holds no non-NULL value
+        return gpuq.project_binop_nullable(total, "/", b=gpuq.cast_i64_f64(cnt),
+                                           a_validity=tvalid)
+
+    @staticmethod
+    def _eval_value(gpuq, e, frame, val, valid, part_bits):
+        """first_value / last_value: the value and NULL-ness of the frame's
+        first / last row. Under "rows", "range" and the default frame the
+        first row is the partition's; the last row of a RANGE frame is the
+        peer group's, which is not built."""
+        if not isinstance(frame, RowsBetween):
+            if e.fn == "last_value" and frame == "range":
+                raise ValueError(
+                    f"window: last_value({e.col}) under the RANGE frame "
+                    "unsupported (give a ROWS frame)")
+            frame = RowsBetween(None, None if frame == "partition" else 0)
+        return gpuq.window_slide(e.fn, frame.lo, frame.hi, part_bits, val=val,
+                                 validity=valid)
+
+    @staticmethod
+    def _eval_slide(gpuq, e, frame, val, valid, n, part_bits):
+        """an aggregate over a sliding frame (gpuq_window_slide)."""
+        if e.fn != "avg":
+            return gpuq.window_slide(e.fn, frame.lo, frame.hi, part_bits,
+                                     val=val, validity=valid, n=n)
+        if val.dtype != torch.float64:
+            raise ValueError(f"window: avg({e.col}) over {val.dtype} "
+                             "unsupported (float64 columns only)")
+        ws = gpuq.window_slide_workspace(n, frame.lo, frame.hi)
+        total, tvalid = gpuq.window_slide("sum", frame.lo, frame.hi, part_bits,
+                                          val=val, validity=valid, workspace=ws)
+        cnt, _ = gpuq.window_slide("count", frame.lo, frame.hi, part_bits,
+                                   val=val, validity=valid, workspace=ws)
         # x / 0 is NULL: the rows whose frame holds no non-NULL value
         return gpuq.project_binop_nullable(total, "/", b=gpuq.cast_i64_f64(cnt),
                                            a_validity=tvalid)

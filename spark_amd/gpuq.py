@@ -222,6 +222,11 @@ def lib() -> ctypes.CDLL:
         L.gpuq_window_shift.argtypes = [vp, i64, _Col, i64, i32,
                                         ctypes.c_double, i64, vp, vp, vp,
                                         vp, i64]
+        L.gpuq_window_slide_workspace_bytes.restype = i64
+        L.gpuq_window_slide_workspace_bytes.argtypes = [i64, i64, i64]
+        L.gpuq_window_slide.restype = i32
+        L.gpuq_window_slide.argtypes = [vp, i64, i32, _Col, i64, i64, vp, vp, vp,
+                                        vp, i64]
         L.gpuq_profiling.restype = None
         L.gpuq_profiling.argtypes = [i32]
         L.gpuq_kernel_stats_reset.restype = None
@@ -1310,5 +1315,100 @@ def window_shift(val, offset: int, part_bits, validity=None, default=None,
                                    int(default is not None), lit_f, lit_i,
                                    part_bits.data_ptr(), out.data_ptr(),
                                    bits.data_ptr(), workspace.data_ptr(),
+                                   workspace.numel()))
+    return out, bits
+
+
+# ---------------- sliding ROWS BETWEEN frames, first_value / last_value ----
+# the ops gpuq_window_slide takes on top of count / sum / min / max
+WIN_SLIDE_OP = {"first_value": 7, "last_value": 8}
+WIN_SLIDE_MAX_SPAN = 2048            # GPUQ_WIN_SLIDE_MAX_SPAN
+_WIN_UNBOUNDED_PRECEDING = -(1 << 63)
+_WIN_UNBOUNDED_FOLLOWING = (1 << 63) - 1
+
+
+def _slide_ops():
+    ops = {k: WIN_OP[k] for k in ("count", "sum", "min", "max")}
+    ops.update(WIN_SLIDE_OP)
+    return ops
+
+
+def _slide_frame(who: str, lo, hi):
+    """(lo, hi) as the C entry point takes them; None is unbounded."""
+    for name, b in (("lo", lo), ("hi", hi)):
+        if b is None:
+            continue
+        if isinstance(b, bool) or not isinstance(b, int):
+            raise ValueError(f"{who}: {name} must be an int or None, got {b!r}")
+        if not -(1 << 31) <= b < (1 << 31):
+            raise ValueError(f"{who}: {name} {b} does not fit int32")
+    if lo is not None and hi is None:
+        raise ValueError(f"{who}: a finite lo ({lo}) with an unbounded hi is "
+                         "not supported")
+    if lo is not None:
+        if lo > hi:
+            raise ValueError(f"{who}: lo {lo} > hi {hi}")
+        if hi - lo > WIN_SLIDE_MAX_SPAN:
+            raise ValueError(f"{who}: span {hi - lo} exceeds "
+                             f"{WIN_SLIDE_MAX_SPAN}")
+    return (_WIN_UNBOUNDED_PRECEDING if lo is None else lo,
+            _WIN_UNBOUNDED_FOLLOWING if hi is None else hi)
+
+
+def window_slide_workspace(n: int, lo, hi, device="cuda") -> torch.Tensor:
+    clo, chi = _slide_frame("window_slide_workspace", lo, hi)
+    if not 0 <= n <= 0xFFFFFFFF:
+        raise ValueError(f"window_slide_workspace: nrows {n} out of range")
+    return torch.empty(lib().gpuq_window_slide_workspace_bytes(n, clo, chi),
+                       dtype=torch.uint8, device=device)
+
+
+def window_slide(op: str, lo, hi, part_bits, val=None, validity=None,
+                 n: int = None, workspace=None):
+    """One window expression over the frame ROWS BETWEEN lo AND hi: signed row
+    offsets from the current row (negative PRECEDING, positive FOLLOWING),
+    None for UNBOUNDED. Both finite with hi - lo <= WIN_SLIDE_MAX_SPAN, or lo
+    None. op: count (val=None is COUNT(*)), sum / min / max, first_value /
+    last_value. Returns (out, out_validity_or_None): no bitmap for count, and
+    none for sum / min / max over a column without one under a frame that
+    cannot be empty (lo <= 0 <= hi). n is taken from val and must be given
+    without it."""
+    ops = _slide_ops()
+    if op not in ops:
+        raise ValueError(f"window_slide: bad op {op!r}")
+    clo, chi = _slide_frame("window_slide", lo, hi)
+    if val is None:
+        if validity is not None:
+            raise ValueError("window_slide: validity without a column")
+        if op != "count":
+            raise ValueError(f"window_slide: {op} needs a column")
+        if n is None:
+            raise ValueError("window_slide: n is needed without a column")
+    else:
+        if val.dtype not in (torch.int64, torch.float64):
+            raise ValueError(f"window_slide: unsupported dtype {val.dtype}")
+        if n is not None and n != val.numel():
+            raise ValueError("window_slide: n differs from the column length")
+        n = val.numel()
+    if not 0 <= n <= 0xFFFFFFFF:
+        raise ValueError(f"window_slide: nrows {n} out of range")
+    _check_bitmaps("window_slide", n, part_bits)
+    dev = part_bits.device
+    need = lib().gpuq_window_slide_workspace_bytes(n, clo, chi)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.numel() < need:
+        raise ValueError(f"window_slide: workspace {workspace.numel()} < {need}")
+    out_dtype = torch.int64 if op == "count" else val.dtype
+    out = torch.empty(n, dtype=out_dtype, device=dev)
+    can_be_empty = (lo is not None and lo > 0) or (hi is not None and hi < 0)
+    bits = None
+    if op in WIN_SLIDE_OP or (op != "count" and (validity is not None
+                                                 or can_be_empty)):
+        bits = torch.empty(_bitmap_bytes(n), dtype=torch.uint8, device=dev)
+    col = _col(val, validity) if val is not None else _Col(None, None, GPUQ_INT64)
+    _check(lib().gpuq_window_slide(_stream(), n, ops[op], col, clo, chi,
+                                   part_bits.data_ptr(), out.data_ptr(),
+                                   _dp(bits), workspace.data_ptr(),
                                    workspace.numel()))
     return out, bits
