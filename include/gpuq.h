@@ -249,8 +249,11 @@ int gpuq_hash_agg_partitioned(void* stream, int64_t nrows,
  * spec_ops[j]: 0=SUM(float64 col), 1=COUNT(col), 2=COUNT(*),
  * 3=SUM(int64 col) -> int64 (Sum.scala LongType result; non-ansi
  * overflow wraps), 4=MIN(int64), 5=MAX(int64), 6=MIN(float64),
- * 7=MAX(float64) (Min/Max.scala; float ordering = Java Double.compare:
- * NaN greatest, -0.0 < 0.0);
+ * 7=MAX(float64) (Min/Max.scala; float64 order = the sort's and the window
+ * functions': NaN greatest and all NaNs equal, -0.0 == 0.0; a zero result
+ * is emitted as +0.0 and a NaN result as the canonical NaN. This deviates
+ * from Spark's Double.compare, which puts -0.0 below 0.0: a group whose
+ * extreme is -0.0 returns +0.0 here and -0.0 in Spark);
  * up to 12 specs; spec_cols[j] indexes vals[] (ignored for COUNT(*)). out_accs[j] is a
  * device array per spec: f64 for SUM_F64/MIN_F64/MAX_F64, i64 otherwise.
  * Small tables (cap*(1+nspecs)*8 <= 64 KB) aggregate per-block in LDS

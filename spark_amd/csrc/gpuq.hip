@@ -2733,7 +2733,11 @@ void k_agg_build_lds(int64_t n, const int64_t* keys, const uint8_t* kvalid,
     unsigned long long k = lt[3 * j];
     if (k == AGG_EMPTY) continue;
     uint64_t slot = ((uint32_t)mm3_hash_long((int64_t)k, 42)) & (uint64_t)cap_mask;
-    for (;;) {
+    /* the global table can be full of other blocks' keys even when no
+     * block's own table overflowed: bound the probe and report, as the
+     * direct build does, instead of probing forever */
+    bool placed = true;
+    for (int64_t probes = 0;; probes++) {
       unsigned long long cur = __hip_atomic_load(&tab[SLOT * slot], __ATOMIC_RELAXED,
                                                  __HIP_MEMORY_SCOPE_AGENT);
       if (cur == k) break;
@@ -2742,7 +2746,9 @@ void k_agg_build_lds(int64_t n, const int64_t* keys, const uint8_t* kvalid,
         if (prev == AGG_EMPTY || prev == k) break;
       }
       slot = (slot + 1) & (uint64_t)cap_mask;
+      if (probes > cap_mask) { atomicMax(&sp->overflow, 1ull); placed = false; break; }
     }
+    if (!placed) continue;
     if (OPS & AGG_OP_SUM)
       atomicAdd((double*)&tab[SLOT * slot + 1],
                 __longlong_as_double((long long)lt[3 * j + 1]));
@@ -4073,10 +4079,14 @@ struct agg_cols { const double* p[AGG_MAX_SPECS]; };
  * expressions): 0=SUM_F64 1=COUNT(col) 2=COUNT(*) 3=SUM_I64(wrapping)
  * 4=MIN_I64 5=MAX_I64 6=MIN_F64 7=MAX_F64. MIN/MAX accumulators hold the
  * monotone u64 encoding (encode_i64/encode_f64) so u64 atomicMin/atomicMax
- * realize the reference ordering incl. NaN-greatest and -0.0 < 0.0; the
- * compact pass decodes. All value ops skip NULL rows; an all-NULL group's
- * acc stays at its init value — callers discriminate via a paired COUNT
- * (Sum/Min/Max evaluate to NULL iff no non-null input).
+ * realize the float64 order the sort and the window functions use: NaN
+ * greatest and all NaNs equal, -0.0 == 0.0 (encode_f64 folds -0.0 to +0.0
+ * and every NaN to the canonical one). The compact pass decodes, so a zero
+ * result is +0.0 and a NaN result the canonical NaN. Spark's Double.compare
+ * puts -0.0 below 0.0 and would return -0.0 for a group whose extreme is
+ * -0.0; here that group returns +0.0. All value ops skip NULL rows; an
+ * all-NULL group's acc stays at its init value — callers discriminate via a
+ * paired COUNT (Sum/Min/Max evaluate to NULL iff no non-null input).
  * 8=SUM_DEC128 9=DEC128_HI 10=MERGE_DEC128: exact 128-bit SUM of scaled-
  * decimal int64 values (Sum.scala's Decimal path, result
  * decimal(min(38,p+10),s)). The accumulator is TWO adjacent words (lo, hi):
@@ -4244,7 +4254,10 @@ void k_aggm_build(int64_t n, const int64_t* keys, const uint8_t* kvalid,
       unsigned long long k = lt[(int64_t)stride * sI];
       if (k == AGG_EMPTY) continue;
       uint64_t slot = ((uint32_t)mm3_hash_long((int64_t)k, 42)) & (uint64_t)cap_mask;
-      for (;;) {
+      /* bounded like the build probe: the global table can fill up with
+       * other blocks' keys although no block's own table overflowed */
+      bool placed = true;
+      for (int64_t probes = 0;; probes++) {
         unsigned long long cur = __hip_atomic_load(&tab[(int64_t)stride * slot],
                                                    __ATOMIC_RELAXED,
                                                    __HIP_MEMORY_SCOPE_AGENT);
@@ -4254,7 +4267,9 @@ void k_aggm_build(int64_t n, const int64_t* keys, const uint8_t* kvalid,
           if (prev == AGG_EMPTY || prev == k) break;
         }
         slot = (slot + 1) & (uint64_t)cap_mask;
+        if (probes > cap_mask) { atomicMax(&sp->overflow, 1ull); placed = false; break; }
       }
+      if (!placed) continue;
       for (int j = 0; j < nspecs; j++)
         aggm_merge_acc(&tab[(int64_t)stride * slot + 1 + j], ops.op[j],
                        lt[(int64_t)stride * sI + 1 + j]);
