@@ -358,12 +358,12 @@ int gpuq_range_partition_perm(void* stream, int64_t nrows, gpuq_col key,
 /* ---------------------------------------------------------------- */
 
 int64_t gpuq_join_build_workspace_bytes(int64_t build_rows, int64_t capacity);
+/* The probe needs no workspace of its own: always 0 (kept for the ABI). */
 int64_t gpuq_join_probe_workspace_bytes(int64_t probe_rows);
 
 /* Build the hash table over the build-side key column. capacity: power of
- * two >= ~1.6*build_rows. The workspace holds the table + chains (and, for
- * large NULL-free tables, the hash-ordered copy of the build side that
- * keeps probes L3-local) and must stay alive through probes. */
+ * two >= ~1.6*build_rows. The workspace holds the table + chains and must
+ * stay alive through probes. */
 int gpuq_join_build_i64(void* stream, int64_t build_rows, gpuq_col build_key,
                         void* workspace, int64_t capacity);
 
@@ -371,8 +371,8 @@ int gpuq_join_build_i64(void* stream, int64_t build_rows, gpuq_col build_key,
  * caller's buffers (out_cap entries each); *out_nmatches returns the total
  * match count. If the count exceeds out_cap, returns GPUQ_ERR_OVERFLOW
  * after setting *out_nmatches (call again with bigger buffers).
- * probe_workspace (gpuq_join_probe_workspace_bytes) enables the
- * hash-ordered probe stream; pass NULL to probe in input order. */
+ * probe_workspace / probe_workspace_bytes are accepted and ignored (they
+ * fed a hash-ordered probe stream that was retired); pass NULL and 0. */
 /* join_type (ShuffledHashJoinExec.scala joinType dispatch): 0=Inner,
  * 1=probe-side Outer (unmatched probe rows pair with build rid 0xFFFFFFFF
  * => NULL build columns; gather with gpuq_gather_nullable), 2=LeftSemi

@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/gpuq.h"
 
@@ -518,9 +519,7 @@ __global__ void k_encode(int64_t n, const void* keys, const uint32_t* rowmap,
 }
 
 /* ---- ranked scatter pass ----
- * BIN_MODE 0: digit = (key >> shift) & 0xff  (radix sort pass)
- * BIN_MODE 2: digit = top 8 bits of Murmur3(key,42) (hash-order
- *             bucketing for the locality-ordered hash join)             */
+ * BIN_MODE 0: digit = (key >> shift) & 0xff  (radix sort pass)          */
 struct scatter_geom { int block, items; };
 static scatter_geom get_sort_geom(void);
 
@@ -528,10 +527,6 @@ template <int BIN_MODE>
 DEV int compute_bin(uint64_t key, int shift, int nparts) {
   (void)nparts;
   if (BIN_MODE == 0) return (int)((key >> shift) & 0xff);
-  if (BIN_MODE == 2)
-    /* top 8 bits of Murmur3(key,42) — hash-order bucketing so a bucketed
-     * stream sweeps a hash-ordered table monotonically (join) */
-    return (int)(((uint32_t)mm3_hash_long((int64_t)key, 42)) >> 24);
   /* BIN_MODE 3: byte `shift/8` of the TOP-16 murmur bits (two stable
    * passes order rows by a 16-bit hash bucket — partitioned aggregation) */
   return (int)((((uint32_t)mm3_hash_long((int64_t)key, 42)) >> (16 + shift)) & 0xff);
@@ -2833,21 +2828,22 @@ extern "C" int gpuq_hash_agg_i64_f64(void* stream, int64_t n,
  *
  * Locality design (MI355X: random HBM lines are ~7x slower than L3-resident
  * access — measured in tools/diag_hash.py): the slot index is the TOP bits
- * of Murmur3(key,42) (multiplicative map, monotone in hash), and when keys
- * have no NULLs both sides are first radix-partitioned into hash order
- * (one ranked-scatter pass, BIN_MODE 2). Blocks then process contiguous
- * chunks of the hash-ordered stream, so the live table region at any
- * instant is a small hash-contiguous window that stays L3-resident, and
- * next[]/rid side arrays are bucket-local. Probe reserves output space
- * with one wave-aggregated atomic.
+ * of Murmur3(key,42) (multiplicative map, monotone in hash). The table is
+ * flat and both sides are streamed in row order: radix-partitioning them
+ * into hash order first was measured as net overhead once the output
+ * cursor stopped being the bottleneck (the probe is latency-bound, not
+ * line-refetch-bound) and was removed. Probe reserves output space with
+ * one atomic per block.
  */
 
 #define JOIN_NIL 0xFFFFFFFFu
 #ifndef JOIN_CHUNK
 #define JOIN_CHUNK 4096
 #endif
+#define JOIN_BLOCK 256   /* threads per build / probe block */
 
-struct join_sp { unsigned int m1_head; unsigned int bucketed; unsigned long long cursor; };
+/* cursor sits at offset 8 (its natural alignment): joink_sp embeds this */
+struct join_sp { unsigned int m1_head; unsigned long long cursor; };
 
 /* hash -> slot: monotone multiplicative map onto [0, cap) */
 DEV uint64_t join_slot(int64_t key, int64_t cap_mask) {
@@ -2859,18 +2855,10 @@ struct join_ws {
   unsigned long long* slots;   /* 2 u64 per slot: [key][head|pad] */
   unsigned int* next;
   unsigned long long* matched; /* build-row matched bits (full outer) */
-  unsigned int* brid;          /* partitioned row id map (bucketed path) */
-  uint64_t* pk_a; uint32_t* pi_a;   /* partition scratch: pairs in */
-  uint64_t* pk_b;                   /* partitioned keys out (ids go to brid) */
-  uint32_t* hist; uint32_t* hist_scan; uint32_t* block_sums;
   join_sp* sp;
 };
 
 static void join_ws_layout(int64_t cap, int64_t brows, join_ws* w, char* base, int64_t* total) {
-  int tile = get_sort_geom().block * get_sort_geom().items;
-  int64_t nb = sort_nblocks(brows, tile);
-  int64_t hist_n = 256 * nb;
-  int64_t scan_blocks = (hist_n + SCAN_TILE - 1) / SCAN_TILE + 1;
   int64_t off = 0;
   auto take = [&](int64_t bytes) {
     char* p = base ? base + off : nullptr;
@@ -2880,13 +2868,6 @@ static void join_ws_layout(int64_t cap, int64_t brows, join_ws* w, char* base, i
   w->slots = (unsigned long long*)take(cap * 16);
   w->next = (unsigned int*)take(brows * 4);
   w->matched = (unsigned long long*)take(((brows + 63) / 64) * 8);
-  w->brid = (unsigned int*)take(brows * 4);
-  w->pk_a = (uint64_t*)take(brows * 8);
-  w->pi_a = (uint32_t*)take(brows * 4);
-  w->pk_b = (uint64_t*)take(brows * 8);
-  w->hist = (uint32_t*)take(hist_n * 4);
-  w->hist_scan = (uint32_t*)take(hist_n * 4);
-  w->block_sums = (uint32_t*)take(scan_blocks * 4);
   w->sp = (join_sp*)take(sizeof(join_sp));
   *total = off;
 }
@@ -2897,73 +2878,10 @@ extern "C" int64_t gpuq_join_build_workspace_bytes(int64_t brows, int64_t cap) {
   return total;
 }
 
-/* probe-side scratch (hash-ordered probe stream) */
-struct probe_ws {
-  uint64_t* pk_a; uint32_t* pi_a;
-  uint64_t* pk_b; uint32_t* pi_b;
-  uint32_t* hist; uint32_t* hist_scan; uint32_t* block_sums;
-};
-
-static void probe_ws_layout(int64_t prows, probe_ws* w, char* base, int64_t* total) {
-  int tile = get_sort_geom().block * get_sort_geom().items;
-  int64_t nb = sort_nblocks(prows, tile);
-  int64_t hist_n = 256 * nb;
-  int64_t scan_blocks = (hist_n + SCAN_TILE - 1) / SCAN_TILE + 1;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~255LL;
-    return p;
-  };
-  w->pk_a = (uint64_t*)take(prows * 8);
-  w->pi_a = (uint32_t*)take(prows * 4);
-  w->pk_b = (uint64_t*)take(prows * 8);
-  w->pi_b = (uint32_t*)take(prows * 4);
-  w->hist = (uint32_t*)take(hist_n * 4);
-  w->hist_scan = (uint32_t*)take(hist_n * 4);
-  w->block_sums = (uint32_t*)take(scan_blocks * 4);
-  *total = off;
-}
-
+/* the probe needs no workspace of its own (kept for the ABI) */
 extern "C" int64_t gpuq_join_probe_workspace_bytes(int64_t prows) {
-  probe_ws w; int64_t total;
-  probe_ws_layout(prows, &w, nullptr, &total);
-  return total;
-}
-
-__global__ void k_make_pairs(int64_t n, const int64_t* keys, uint64_t* out_k,
-                             uint32_t* out_i) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    out_k[i] = (uint64_t)keys[i];
-    out_i[i] = (uint32_t)i;
-  }
-}
-
-/* one hash-order partition pass over (key, rowid) pairs */
-static int hash_order_pairs(hipStream_t s, int64_t n, const int64_t* keys,
-                            uint64_t* tmp_k, uint32_t* tmp_i,
-                            uint64_t* out_k, uint32_t* out_i,
-                            uint32_t* hist, uint32_t* hist_scan,
-                            uint32_t* block_sums) {
-  scatter_geom geom = get_sort_geom();
-  int tile = geom.block * geom.items;
-  int64_t nb = sort_nblocks(n, tile);
-  k_make_pairs<<<grid1d(n), 256, 0, s>>>(n, keys, tmp_k, tmp_i);
-  HIP_TRY(hipGetLastError());
-  { hipEvent_t _pe = prof_begin(s);
-  k_radix_hist<2><<<dim3((uint32_t)nb), 256, 0, s>>>(n, tmp_k, 0, hist, (int)nb, tile);
-  prof_end("join_part_hist", s, _pe); }
-  HIP_TRY(hipGetLastError());
-  int rc = exclusive_scan_u32(s, 256 * nb, hist, hist_scan, block_sums);
-  if (rc) return rc;
-  { hipEvent_t _pe = prof_begin(s);
-  launch_scatter<2, false>(s, geom, nb, n, tmp_k, tmp_i, out_k, out_i,
-                           hist_scan, 0, 0, nullptr, nullptr, nullptr, 0);
-  prof_end("join_part_scatter", s, _pe); }
-  HIP_TRY(hipGetLastError());
-  return GPUQ_OK;
+  (void)prows;
+  return 0;
 }
 
 /* chain-head word: bit 31 = MULTI (slot holds >1 row) so single-match
@@ -2984,8 +2902,7 @@ DEV void join_push_head(unsigned int* headp, unsigned int i, unsigned int* next)
   }
 }
 
-/* contiguous-chunk mapping: block b owns rows [b*CHUNK, (b+1)*CHUNK) so the
- * live window of a hash-ordered stream is hash-contiguous (L3-resident) */
+/* contiguous-chunk mapping: block b owns rows [b*CHUNK, (b+1)*CHUNK) */
 __global__ void k_join_build(int64_t n, const int64_t* keys, const uint8_t* kvalid,
                              unsigned long long* slots, unsigned int* next,
                              join_sp* sp, int64_t cap_mask) {
@@ -3028,106 +2945,151 @@ DEV uint32_t jt_emit_count(int jt, uint32_t m) {
   return m;
 }
 
-template <int JT>
-__global__ void k_join_probe(int64_t n, const int64_t* keys, const uint8_t* kvalid,
-                             const unsigned long long* slots, const unsigned int* next,
-                             const unsigned int* brid_map, const unsigned int* prid_map,
-                             join_sp* sp, int64_t cap_mask,
-                             uint32_t* out_p, uint32_t* out_b, int64_t out_cap,
-                             unsigned long long* matched = nullptr) {
-  constexpr int ROUNDS = JOIN_CHUNK / 256;
+/* ---- probe skeleton: k_join_probe, k_joink_probe and k_joink_probe_cond
+ * differ only in how a row finds its chain head (join_find_head /
+ * joink_find_head) and in which chain entries count as matches (the accept
+ * functor: all of them, or joinc_pass) ----
+ *
+ * A block of JOIN_BLOCK threads owns CHUNK consecutive probe rows and takes
+ * them in CHUNK / JOIN_BLOCK rounds. Phase A looks every row up, counts its
+ * matches and keeps the first two (join_collect); ONE output-cursor atomic
+ * per block then reserves the block's output (join_reserve: a single global
+ * cursor word saturates near ~88 updates/us — the per-wave-iteration
+ * version was the whole kernel's bottleneck); phase B emits (join_emit_row).
+ * The kernels hold nothing but the two round loops. */
+
+struct join_accept_all {
+  __device__ bool operator()(int64_t, unsigned int) const { return true; }
+};
+
+/* Chain collect for probe row i: cnt = accepted entries of the chain at
+ * `head`, c0 / c1 = the first two. Semi / anti need only "is there one", so
+ * their walk stops at the first. */
+template <int JT, class Accept>
+DEV void join_collect(unsigned int head, int64_t i, const unsigned int* next,
+                      unsigned long long* matched, Accept accept,
+                      uint32_t* cnt, unsigned int* c0, unsigned int* c1) {
+  uint32_t m = 0;
+  unsigned int m0 = JOIN_NIL, m1 = JOIN_NIL;
+  /* a head without JOIN_MULTI is a one-candidate chain: next[] untouched */
+  const bool multi = head != JOIN_NIL && (head & JOIN_MULTI);
+  for (unsigned int b = head == JOIN_NIL ? JOIN_NIL : (head & ~JOIN_MULTI);
+       b != JOIN_NIL; b = multi ? next[b] : JOIN_NIL) {
+    if (!accept(i, b)) continue;
+    if (m == 0) m0 = b; else if (m == 1) m1 = b;
+    m++;
+    if (JT == 4) atomicOr(&matched[b >> 6], 1ull << (b & 63));
+    if (JT == 2 || JT == 3 || JT == 5) break;
+  }
+  *cnt = m; *c0 = m0; *c1 = m1;
+}
+
+/* Block-level reservation of lane_total output slots per lane: returns this
+ * lane's first slot (emit order within the block is arbitrary — join output
+ * order is nondeterministic by contract). */
+DEV int64_t join_reserve(uint32_t lane_total, unsigned long long* cursor) {
   __shared__ unsigned long long block_base;
-  __shared__ uint32_t wtot[JOIN_CHUNK / 256 > 4 ? 16 : 16];
+  __shared__ uint32_t wtot[JOIN_BLOCK / WAVE];
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
-  const int64_t base = (int64_t)blockIdx.x * JOIN_CHUNK;
+  uint32_t incl = wave_inclusive_scan(lane_total);
+  if (lane == WAVE - 1) wtot[wave] = incl;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (int w = 0; w < JOIN_BLOCK / WAVE; w++) {
+      uint32_t t = wtot[w]; wtot[w] = tot; tot += t;
+    }
+    block_base = tot ? atomicAdd(cursor, (unsigned long long)tot) : 0;
+  }
+  __syncthreads();
+  return (int64_t)block_base + wtot[wave] + (incl - lane_total);
+}
 
-  /* phase A: all lookups; match counts + first two matches stay in
-   * registers. ONE output-cursor atomic per block (a single global cursor
-   * word saturates near ~88 updates/us — the per-wave-iteration version
-   * was the whole kernel's bottleneck). */
+/* Emit probe row i's pairs from slot o on and advance o by what phase A
+ * reserved for it. A row with more than two matches walks the rest of its
+ * chain again, from next[c1] on, re-asking `accept`: both walks follow
+ * next[] over an immutable table, so this one finds exactly the cnt - 2
+ * entries phase A counted after c1. */
+template <int JT, class Accept>
+DEV void join_emit_row(int64_t i, bool in_range, uint32_t cnt, unsigned int c0,
+                       unsigned int c1, const unsigned int* next, Accept accept,
+                       int64_t& o, uint32_t* out_p, uint32_t* out_b,
+                       int64_t out_cap) {
+  if (JT != 0) {
+    if (!in_range || !jt_emit_count(JT, cnt)) return;
+    if (JT == 2 || JT == 3 || JT == 5 || cnt == 0) {
+      /* semi/anti emit the probe row once; outer's unmatched row pairs
+       * with NIL (NULL build columns downstream) */
+      if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = JOIN_NIL; }
+      o++;
+      return;
+    }
+  }
+  if (!cnt) return;
+  if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = c0; }
+  o++;
+  if (cnt >= 2) {
+    if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = c1; }
+    o++;
+  }
+  if (cnt > 2) {
+    /* o advances by the reserved cnt - 2 whatever the walk finds */
+    const int64_t o_end = o + (cnt - 2);
+    for (unsigned int b = next[c1]; b != JOIN_NIL && o < o_end; b = next[b]) {
+      if (!accept(i, b)) continue;
+      if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = b; }
+      o++;
+    }
+    o = o_end;
+  }
+}
+
+/* single-key lookup of a non-NULL key: open-address walk from join_slot, the
+ * m1_head chain for real -1 keys (the slots' EMPTY sentinel) */
+DEV unsigned int join_find_head(int64_t k, const unsigned long long* slots,
+                                const join_sp* sp, int64_t cap_mask) {
+  if ((unsigned long long)k == AGG_EMPTY) return sp->m1_head;
+  uint64_t slot = join_slot(k, cap_mask);
+  for (;;) {
+    unsigned long long cur = slots[2 * slot];
+    if (cur == AGG_EMPTY) return JOIN_NIL;
+    if (cur == (unsigned long long)k) return (unsigned int)slots[2 * slot + 1];
+    slot = (slot + 1) & (uint64_t)cap_mask;
+  }
+}
+
+template <int JT>
+__global__ __launch_bounds__(JOIN_BLOCK)
+void k_join_probe(int64_t n, const int64_t* keys, const uint8_t* kvalid,
+                  const unsigned long long* slots, const unsigned int* next,
+                  join_sp* sp, int64_t cap_mask,
+                  uint32_t* out_p, uint32_t* out_b, int64_t out_cap,
+                  unsigned long long* matched) {
+  constexpr int ROUNDS = JOIN_CHUNK / JOIN_BLOCK;
+  const int64_t base = (int64_t)blockIdx.x * JOIN_CHUNK + threadIdx.x;
+  const join_accept_all accept;
   uint32_t cnt[ROUNDS];
   unsigned int c0[ROUNDS], c1[ROUNDS];
   uint32_t lane_total = 0;
   for (int r = 0; r < ROUNDS; r++) {
-    int64_t i = base + r * 256 + threadIdx.x;
-    unsigned int head = JOIN_NIL;
-    if (i < n && bit_valid(kvalid, i)) {
-      int64_t k = keys[i];
-      if ((unsigned long long)k == AGG_EMPTY) {
-        head = sp->m1_head;
-      } else {
-        uint64_t slot = join_slot(k, cap_mask);
-        for (;;) {
-          unsigned long long cur = slots[2 * slot];
-          if (cur == AGG_EMPTY) break;
-          if (cur == (unsigned long long)k) {
-            head = (unsigned int)slots[2 * slot + 1];
-            break;
-          }
-          slot = (slot + 1) & (uint64_t)cap_mask;
-        }
-      }
-    }
-    cnt[r] = 0; c0[r] = JOIN_NIL; c1[r] = JOIN_NIL;
-    if (head != JOIN_NIL) {
-      if (!(head & JOIN_MULTI)) {
-        c0[r] = head; cnt[r] = 1;
-        if (JT == 4) atomicOr(&matched[head >> 6], 1ull << (head & 63));
-      } else {
-        for (unsigned int b = head & ~JOIN_MULTI; b != JOIN_NIL; b = next[b]) {
-          if (cnt[r] == 0) c0[r] = b; else if (cnt[r] == 1) c1[r] = b;
-          cnt[r]++;
-          if (JT == 4) atomicOr(&matched[b >> 6], 1ull << (b & 63));
-        }
-      }
-    }
-    if (JT == 5 && i < n && !bit_valid(kvalid, i))
+    const int64_t i = base + r * JOIN_BLOCK;
+    const bool valid = i < n && bit_valid(kvalid, i);
+    const unsigned int head =
+        valid ? join_find_head(keys[i], slots, sp, cap_mask) : JOIN_NIL;
+    join_collect<JT>(head, i, next, matched, accept, &cnt[r], &c0[r], &c1[r]);
+    if (JT == 5 && i < n && !valid)
       cnt[r] = 1;  /* null-aware anti: NULL NOT IN (non-empty) is unknown
                     * -> the row is filtered (treated as matched);
                     * BroadcastHashJoinExec.scala:137 NAAJ semantics */
     if (JT == 0) lane_total += cnt[r];
     else if (i < n) lane_total += jt_emit_count(JT, cnt[r]);
   }
-  /* phase B: block-level reservation (emit order within the block is
-   * arbitrary — join output order is nondeterministic by contract) */
-  uint32_t incl = wave_inclusive_scan(lane_total);
-  if (lane == WAVE - 1) wtot[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t tot = 0;
-    for (int w = 0; w < (int)(blockDim.x / WAVE); w++) {
-      uint32_t t = wtot[w]; wtot[w] = tot; tot += t;
-    }
-    block_base = tot ? atomicAdd(&sp->cursor, (unsigned long long)tot) : 0;
-  }
-  __syncthreads();
-  int64_t o = (int64_t)block_base + wtot[wave] + (incl - lane_total);
+  int64_t o = join_reserve(lane_total, &sp->cursor);
   for (int r = 0; r < ROUNDS; r++) {
-    int64_t i = base + r * 256 + threadIdx.x;
-    if (JT != 0) {
-      if (i >= n || !jt_emit_count(JT, cnt[r])) continue;
-      uint32_t pr = prid_map ? prid_map[i] : (uint32_t)i;
-      if (JT == 2 || JT == 3 || JT == 5 || cnt[r] == 0) {
-        /* semi/anti emit the probe row once; outer's unmatched row pairs
-         * with NIL (NULL build columns downstream) */
-        if (o < out_cap) { out_p[o] = pr; out_b[o] = JOIN_NIL; }
-        o++;
-        continue;
-      }
-    }
-    if (!cnt[r]) continue;
-    uint32_t pr = prid_map ? prid_map[i] : (uint32_t)i;
-    if (o < out_cap) { out_p[o] = pr; out_b[o] = brid_map ? brid_map[c0[r]] : c0[r]; }
-    o++;
-    if (cnt[r] >= 2) {
-      if (o < out_cap) { out_p[o] = pr; out_b[o] = brid_map ? brid_map[c1[r]] : c1[r]; }
-      o++;
-      unsigned int b = (cnt[r] > 2) ? next[c1[r]] : JOIN_NIL;
-      for (uint32_t j = 2; j < cnt[r]; j++, b = next[b], o++) {
-        if (o < out_cap) { out_p[o] = pr; out_b[o] = brid_map ? brid_map[b] : b; }
-      }
-    }
+    const int64_t i = base + r * JOIN_BLOCK;
+    join_emit_row<JT>(i, i < n, cnt[r], c0[r], c1[r], next, accept, o,
+                      out_p, out_b, out_cap);
   }
 }
 
@@ -3136,7 +3098,6 @@ __global__ void k_join_probe(int64_t n, const int64_t* keys, const uint8_t* kval
  * rows, which are never inserted and so never matched). */
 __global__ void k_join_unmatched_build(int64_t brows,
                                        const unsigned long long* matched,
-                                       const unsigned int* brid_map,
                                        join_sp* sp,
                                        uint32_t* out_p, uint32_t* out_b,
                                        int64_t out_cap) {
@@ -3157,9 +3118,47 @@ __global__ void k_join_unmatched_build(int64_t brows,
     int64_t o = (int64_t)base + __popcll(m & ((1ULL << lane) - 1));
     if (o < out_cap) {
       out_p[o] = JOIN_NIL;
-      out_b[o] = brid_map ? brid_map[i] : (unsigned int)i;
+      out_b[o] = (unsigned int)i;
     }
   }
+}
+
+/* Host side of every probe: reset the output cursor and, if there are probe
+ * rows, launch the kernel instantiation for join_type (which the caller has
+ * checked against 0..MAX_JT) as launch(std::integral_constant<int, JT>()). */
+template <int MAX_JT, class Launch>
+static int join_launch_probe(hipStream_t s, join_sp* sp, int64_t prows,
+                             int32_t join_type, const char* tag, Launch launch) {
+  HIP_TRY(hipMemsetAsync(&sp->cursor, 0, 8, s));
+  if (prows <= 0) return GPUQ_OK;
+  hipEvent_t _pe = prof_begin(s);
+  switch (join_type) {
+    case 1: launch(std::integral_constant<int, 1>()); break;
+    case 2: launch(std::integral_constant<int, 2>()); break;
+    case 3: launch(std::integral_constant<int, 3>()); break;
+    case 4: launch(std::integral_constant<int, 4>()); break;
+    case 5:
+      if constexpr (MAX_JT >= 5) launch(std::integral_constant<int, 5>());
+      break;
+    default: launch(std::integral_constant<int, 0>()); break;
+  }
+  prof_end(tag, s, _pe);
+  HIP_TRY(hipGetLastError());
+  return GPUQ_OK;
+}
+
+/* read the output cursor back; a count above out_cap is an error the caller
+ * answers with a larger buffer */
+static int join_read_count(hipStream_t s, const join_sp* sp, const char* who,
+                           const char* what, int64_t out_cap, int64_t* out_n) {
+  unsigned long long cursor;
+  HIP_TRY(hipMemcpyAsync(&cursor, &sp->cursor, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *out_n = (int64_t)cursor;
+  if ((int64_t)cursor > out_cap)
+    FAIL(GPUQ_ERR_OVERFLOW, "%s: %lld %s exceed out_cap %lld", who,
+         (long long)cursor, what, (long long)out_cap);
+  return GPUQ_OK;
 }
 
 extern "C" int gpuq_join_build_i64(void* stream, int64_t brows, gpuq_col bkey,
@@ -3174,34 +3173,19 @@ extern "C" int gpuq_join_build_i64(void* stream, int64_t brows, gpuq_col bkey,
   HIP_TRY(hipMemsetAsync(w.slots, 0xFF, cap * 16, s));  /* keys=-1, heads=NIL */
   HIP_TRY(hipMemsetAsync(w.matched, 0, ((brows + 63) / 64) * 8, s));
   HIP_TRY(hipMemsetAsync(w.sp, 0xFF, 4, s));            /* m1_head = NIL */
-  HIP_TRY(hipMemsetAsync(&w.sp->bucketed, 0, 4, s));
   HIP_TRY(hipMemsetAsync(&w.sp->cursor, 0, 8, s));
   if (brows == 0) return GPUQ_OK;
-  /* bucketed (hash-ordered) path when there are no NULLs and the table is
-   * past L3 size; flat otherwise */
-  /* hash-order bucketing measured as net overhead once the output-cursor
-   * bottleneck was removed (probe is latency-, not line-refetch-bound);
-   * kept behind an opt-in env for future asymmetric shapes */
-  bool bucketed = bkey.validity == nullptr && cap * 16 > (256LL << 20) &&
-                  getenv("GPUQ_BUCKET_JOIN") != nullptr;
-  const int64_t* keys = (const int64_t*)bkey.data;
-  if (bucketed) {
-    int rc = hash_order_pairs(s, brows, keys, w.pk_a, w.pi_a, w.pk_b, w.brid,
-                              w.hist, w.hist_scan, w.block_sums);
-    if (rc) return rc;
-    keys = (const int64_t*)w.pk_b;
-    HIP_TRY(hipMemsetAsync(&w.sp->bucketed, 1, 1, s));
-  }
   int64_t nchunks = (brows + JOIN_CHUNK - 1) / JOIN_CHUNK;
   { hipEvent_t _pe = prof_begin(s);
   k_join_build<<<dim3((uint32_t)nchunks), 256, 0, s>>>(
-      brows, keys, bucketed ? nullptr : bkey.validity, w.slots, w.next, w.sp,
+      brows, (const int64_t*)bkey.data, bkey.validity, w.slots, w.next, w.sp,
       cap - 1);
   prof_end("join_build", s, _pe); }
   HIP_TRY(hipGetLastError());
   return GPUQ_OK;
 }
 
+/* probe_workspace / probe_ws_bytes are accepted and ignored (ABI) */
 extern "C" int gpuq_join_probe_i64_typed(void* stream, int64_t prows, gpuq_col pkey,
                                    const void* workspace, int64_t cap, int64_t brows,
                                    void* probe_workspace, int64_t probe_ws_bytes,
@@ -3209,82 +3193,26 @@ extern "C" int gpuq_join_probe_i64_typed(void* stream, int64_t prows, gpuq_col p
                                    uint32_t* out_p, uint32_t* out_b,
                                    int64_t out_cap, int64_t* out_nmatches) {
   hipStream_t s = (hipStream_t)stream;
+  (void)probe_workspace; (void)probe_ws_bytes;
   if (join_type < 0 || join_type > 5)
     FAIL(GPUQ_ERR_INVALID, "join: bad join_type %d", join_type);
   if (pkey.dtype != GPUQ_INT64) FAIL(GPUQ_ERR_INVALID, "join: key must be int64");
   join_ws w; int64_t need;
   join_ws_layout(cap, brows, &w, (char*)workspace, &need);
-  HIP_TRY(hipMemsetAsync(&w.sp->cursor, 0, 8, s));
-  if (prows > 0) {
-    join_sp hsp0;
-    HIP_TRY(hipMemcpyAsync(&hsp0, w.sp, sizeof(hsp0), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    bool build_bucketed = hsp0.bucketed != 0;
-    const int64_t* pkeys = (const int64_t*)pkey.data;
-    const uint8_t* pvalid = pkey.validity;
-    const unsigned int* prid_map = nullptr;
-    probe_ws pw;
-    /* order the probe stream by hash too (same locality argument) */
-    bool probe_bucketed = build_bucketed && pvalid == nullptr &&
-                          probe_workspace != nullptr;
-    if (probe_bucketed) {
-      int64_t pneed;
-      probe_ws_layout(prows, &pw, (char*)probe_workspace, &pneed);
-      if (probe_ws_bytes < pneed)
-        FAIL(GPUQ_ERR_INVALID, "join: probe workspace %lld < %lld",
-             (long long)probe_ws_bytes, (long long)pneed);
-      int rc = hash_order_pairs(s, prows, pkeys, pw.pk_a, pw.pi_a, pw.pk_b,
-                                pw.pi_b, pw.hist, pw.hist_scan, pw.block_sums);
-      if (rc) return rc;
-      pkeys = (const int64_t*)pw.pk_b;
-      prid_map = pw.pi_b;
-      pvalid = nullptr;
-    }
-    int64_t nchunks = (prows + JOIN_CHUNK - 1) / JOIN_CHUNK;
-    { hipEvent_t _pe = prof_begin(s);
-    const unsigned int* bm = build_bucketed ? w.brid : nullptr;
-    dim3 jg((uint32_t)nchunks);
-    if (join_type == 1)
-      k_join_probe<1><<<jg, 256, 0, s>>>(prows, pkeys, pvalid, w.slots, w.next,
-                                         bm, prid_map, w.sp, cap - 1, out_p, out_b, out_cap);
-    else if (join_type == 2)
-      k_join_probe<2><<<jg, 256, 0, s>>>(prows, pkeys, pvalid, w.slots, w.next,
-                                         bm, prid_map, w.sp, cap - 1, out_p, out_b, out_cap);
-    else if (join_type == 3)
-      k_join_probe<3><<<jg, 256, 0, s>>>(prows, pkeys, pvalid, w.slots, w.next,
-                                         bm, prid_map, w.sp, cap - 1, out_p, out_b, out_cap);
-    else if (join_type == 4)
-      k_join_probe<4><<<jg, 256, 0, s>>>(prows, pkeys, pvalid, w.slots, w.next,
-                                         bm, prid_map, w.sp, cap - 1, out_p, out_b, out_cap,
-                                         w.matched);
-    else if (join_type == 5)
-      k_join_probe<5><<<jg, 256, 0, s>>>(prows, pkeys, pvalid, w.slots, w.next,
-                                         bm, prid_map, w.sp, cap - 1, out_p, out_b, out_cap);
-    else
-      k_join_probe<0><<<jg, 256, 0, s>>>(prows, pkeys, pvalid, w.slots, w.next,
-                                         bm, prid_map, w.sp, cap - 1, out_p, out_b, out_cap);
-    prof_end("join_probe", s, _pe); }
-    HIP_TRY(hipGetLastError());
-  }
+  dim3 jg((uint32_t)((prows + JOIN_CHUNK - 1) / JOIN_CHUNK));
+  if (int rc = join_launch_probe<5>(s, w.sp, prows, join_type, "join_probe", [&](auto jt) {
+        k_join_probe<decltype(jt)::value><<<jg, JOIN_BLOCK, 0, s>>>(
+            prows, (const int64_t*)pkey.data, pkey.validity, w.slots, w.next,
+            w.sp, cap - 1, out_p, out_b, out_cap, w.matched);
+      })) return rc;
   if (join_type == 4 && brows > 0) {
     /* FullOuter second half; probes with zero rows still emit every
      * build row */
-    join_sp hsp0b;
-    HIP_TRY(hipMemcpyAsync(&hsp0b, w.sp, sizeof(hsp0b), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
     k_join_unmatched_build<<<grid1d(brows), 256, 0, s>>>(
-        brows, w.matched, hsp0b.bucketed ? w.brid : nullptr, w.sp,
-        out_p, out_b, out_cap);
+        brows, w.matched, w.sp, out_p, out_b, out_cap);
     HIP_TRY(hipGetLastError());
   }
-  join_sp hsp;
-  HIP_TRY(hipMemcpyAsync(&hsp, w.sp, sizeof(hsp), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  *out_nmatches = (int64_t)hsp.cursor;
-  if ((int64_t)hsp.cursor > out_cap)
-    FAIL(GPUQ_ERR_OVERFLOW, "join: %lld matches exceed out_cap %lld",
-         (long long)hsp.cursor, (long long)out_cap);
-  return GPUQ_OK;
+  return join_read_count(s, w.sp, "join", "matches", out_cap, out_nmatches);
 }
 
 extern "C" int gpuq_join_probe_i64(void* stream, int64_t prows, gpuq_col pkey,
@@ -3426,7 +3354,7 @@ __global__ void k_joink_init(int64_t cap, int sw, unsigned long long* slots,
     slots[i * sw + 1] = JOINK_HEAD_INIT;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    sp->j.m1_head = JOIN_NIL; sp->j.bucketed = 0; sp->j.cursor = 0;
+    sp->j.m1_head = JOIN_NIL; sp->j.cursor = 0;
     sp->overflow = 0;
   }
 }
@@ -3502,104 +3430,63 @@ void k_joink_build(int64_t n, joink_cols kc, int nkeys, int sw,
   }
 }
 
-/* Same structure as k_join_probe: phase A looks every row up (match counts
- * and the first two matches stay in registers), phase B makes ONE output
- * reservation per block. JT as there, 0-4; a probe row with a NULL in any
- * key column has zero matches. The table was published by an earlier
- * launch, so plain loads suffice. */
+/* composite-key lookup: the slot walk. A row with a NULL in any key column
+ * has no chain. The table was published by an earlier launch, so plain
+ * loads suffice. */
+DEV unsigned int joink_find_head(const joink_cols& kc, int nkeys, int sw,
+                                 const unsigned long long* slots,
+                                 int64_t cap_mask, int64_t i) {
+  unsigned int head = JOIN_NIL;
+  int64_t key[JOINK_MAX_KEYS];
+  uint32_t h; unsigned long long mysig;
+  if (joink_load(kc, nkeys, i, key, &h, &mysig)) {
+    uint64_t slot = h & (uint64_t)cap_mask;
+    /* bounded like the build: a (contract-violating) full table ends the
+     * walk after cap visits instead of circling */
+    for (int64_t visits = 0; visits <= cap_mask; visits++) {
+      const unsigned long long* sl = slots + slot * sw;
+      unsigned long long cur = sl[0];
+      if (cur == JOINK_EMPTY) break;
+      if (cur == mysig) {
+        bool eq = true;
+#pragma unroll
+        for (int c = 0; c < JOINK_MAX_KEYS; c++)
+          if (c < nkeys) eq = eq && sl[2 + c] == (unsigned long long)key[c];
+        if (eq) { head = (unsigned int)sl[1]; break; }
+      }
+      slot = (slot + 1) & (uint64_t)cap_mask;
+    }
+  }
+  return head;
+}
+
+/* The probe skeleton over the composite table; JT 0-4. */
 template <int JT>
-__global__ __launch_bounds__(256)
+__global__ __launch_bounds__(JOIN_BLOCK)
 void k_joink_probe(int64_t n, joink_cols kc, int nkeys, int sw,
                    const unsigned long long* slots, const unsigned int* next,
                    joink_sp* sp, int64_t cap_mask,
                    uint32_t* out_p, uint32_t* out_b, int64_t out_cap,
                    unsigned long long* matched) {
-  constexpr int ROUNDS = JOIN_CHUNK / 256;
-  __shared__ unsigned long long block_base;
-  __shared__ uint32_t wtot[256 / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = threadIdx.x / WAVE;
-  const int64_t base = (int64_t)blockIdx.x * JOIN_CHUNK;
-
+  constexpr int ROUNDS = JOIN_CHUNK / JOIN_BLOCK;
+  const int64_t base = (int64_t)blockIdx.x * JOIN_CHUNK + threadIdx.x;
+  const join_accept_all accept;
   uint32_t cnt[ROUNDS];
   unsigned int c0[ROUNDS], c1[ROUNDS];
   uint32_t lane_total = 0;
   for (int r = 0; r < ROUNDS; r++) {
-    int64_t i = base + r * 256 + threadIdx.x;
-    unsigned int head = JOIN_NIL;
-    int64_t key[JOINK_MAX_KEYS];
-    uint32_t h; unsigned long long mysig;
-    if (i < n && joink_load(kc, nkeys, i, key, &h, &mysig)) {
-      uint64_t slot = h & (uint64_t)cap_mask;
-      /* bounded like the build: a (contract-violating) full table ends the
-       * walk after cap visits instead of circling */
-      for (int64_t visits = 0; visits <= cap_mask; visits++) {
-        const unsigned long long* sl = slots + slot * sw;
-        unsigned long long cur = sl[0];
-        if (cur == JOINK_EMPTY) break;
-        if (cur == mysig) {
-          bool eq = true;
-#pragma unroll
-          for (int c = 0; c < JOINK_MAX_KEYS; c++)
-            if (c < nkeys) eq = eq && sl[2 + c] == (unsigned long long)key[c];
-          if (eq) { head = (unsigned int)sl[1]; break; }
-        }
-        slot = (slot + 1) & (uint64_t)cap_mask;
-      }
-    }
-    cnt[r] = 0; c0[r] = JOIN_NIL; c1[r] = JOIN_NIL;
-    if (head != JOIN_NIL) {
-      if (!(head & JOIN_MULTI)) {
-        c0[r] = head; cnt[r] = 1;
-        if (JT == 4) atomicOr(&matched[head >> 6], 1ull << (head & 63));
-      } else {
-        for (unsigned int b = head & ~JOIN_MULTI; b != JOIN_NIL; b = next[b]) {
-          if (cnt[r] == 0) c0[r] = b; else if (cnt[r] == 1) c1[r] = b;
-          cnt[r]++;
-          if (JT == 4) atomicOr(&matched[b >> 6], 1ull << (b & 63));
-        }
-      }
-    }
+    const int64_t i = base + r * JOIN_BLOCK;
+    const unsigned int head =
+        i < n ? joink_find_head(kc, nkeys, sw, slots, cap_mask, i) : JOIN_NIL;
+    join_collect<JT>(head, i, next, matched, accept, &cnt[r], &c0[r], &c1[r]);
     if (JT == 0) lane_total += cnt[r];
     else if (i < n) lane_total += jt_emit_count(JT, cnt[r]);
   }
-  /* phase B: block-level reservation (emit order within the block is
-   * arbitrary — join output order is nondeterministic by contract) */
-  uint32_t incl = wave_inclusive_scan(lane_total);
-  if (lane == WAVE - 1) wtot[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t tot = 0;
-    for (int w = 0; w < 256 / WAVE; w++) {
-      uint32_t t = wtot[w]; wtot[w] = tot; tot += t;
-    }
-    block_base = tot ? atomicAdd(&sp->j.cursor, (unsigned long long)tot) : 0;
-  }
-  __syncthreads();
-  int64_t o = (int64_t)block_base + wtot[wave] + (incl - lane_total);
+  int64_t o = join_reserve(lane_total, &sp->j.cursor);
   for (int r = 0; r < ROUNDS; r++) {
-    int64_t i = base + r * 256 + threadIdx.x;
-    if (JT != 0) {
-      if (i >= n || !jt_emit_count(JT, cnt[r])) continue;
-      if (JT == 2 || JT == 3 || cnt[r] == 0) {
-        /* semi/anti emit the probe row once; outer's unmatched row pairs
-         * with NIL (NULL build columns downstream) */
-        if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = JOIN_NIL; }
-        o++;
-        continue;
-      }
-    }
-    if (!cnt[r]) continue;
-    if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = c0[r]; }
-    o++;
-    if (cnt[r] >= 2) {
-      if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = c1[r]; }
-      o++;
-      unsigned int b = (cnt[r] > 2) ? next[c1[r]] : JOIN_NIL;
-      for (uint32_t j = 2; j < cnt[r]; j++, b = next[b], o++) {
-        if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = b; }
-      }
-    }
+    const int64_t i = base + r * JOIN_BLOCK;
+    join_emit_row<JT>(i, i < n, cnt[r], c0[r], c1[r], next, accept, o,
+                      out_p, out_b, out_cap);
   }
 }
 
@@ -3655,33 +3542,15 @@ extern "C" int gpuq_join_probe_keys(void* stream, int64_t prows,
   if (int rc = joink_check_cols("join_keys probe", probe_keys, nkeys, &kc)) return rc;
   joink_ws w; int64_t need;
   joink_ws_layout(cap, brows, nkeys, &w, (char*)workspace, &need);
-  HIP_TRY(hipMemsetAsync(&w.sp->j.cursor, 0, 8, s));
-  if (prows > 0) {
-    int sw = joink_stride_words(nkeys);
-    dim3 jg((uint32_t)((prows + JOIN_CHUNK - 1) / JOIN_CHUNK));
-    hipEvent_t _pe = prof_begin(s);
-#define JKP(JT) k_joink_probe<JT><<<jg, 256, 0, s>>>( \
-        prows, kc, nkeys, sw, w.slots, w.next, w.sp, cap - 1, out_p, out_b, \
-        out_cap, w.matched)
-    switch (join_type) {
-      case 1: JKP(1); break;
-      case 2: JKP(2); break;
-      case 3: JKP(3); break;
-      case 4: JKP(4); break;
-      default: JKP(0); break;
-    }
-#undef JKP
-    prof_end("join_keys_probe", s, _pe);
-    HIP_TRY(hipGetLastError());
-  }
-  joink_sp hsp;
-  HIP_TRY(hipMemcpyAsync(&hsp, w.sp, sizeof(hsp), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  *out_nmatches = (int64_t)hsp.j.cursor;
-  if ((int64_t)hsp.j.cursor > out_cap)
-    FAIL(GPUQ_ERR_OVERFLOW, "join_keys probe: %lld matches exceed out_cap %lld",
-         (long long)hsp.j.cursor, (long long)out_cap);
-  return GPUQ_OK;
+  int sw = joink_stride_words(nkeys);
+  dim3 jg((uint32_t)((prows + JOIN_CHUNK - 1) / JOIN_CHUNK));
+  if (int rc = join_launch_probe<4>(s, &w.sp->j, prows, join_type, "join_keys_probe", [&](auto jt) {
+        k_joink_probe<decltype(jt)::value><<<jg, JOIN_BLOCK, 0, s>>>(
+            prows, kc, nkeys, sw, w.slots, w.next, w.sp, cap - 1, out_p, out_b,
+            out_cap, w.matched);
+      })) return rc;
+  return join_read_count(s, &w.sp->j, "join_keys probe", "matches", out_cap,
+                         out_nmatches);
 }
 
 extern "C" int gpuq_join_keys_unmatched_build(void* stream, void* workspace,
@@ -3696,17 +3565,11 @@ extern "C" int gpuq_join_keys_unmatched_build(void* stream, void* workspace,
   HIP_TRY(hipMemsetAsync(&w.sp->j.cursor, 0, 8, s));
   if (brows > 0) {
     k_join_unmatched_build<<<grid1d(brows), 256, 0, s>>>(
-        brows, w.matched, nullptr, &w.sp->j, out_p, out_b, out_cap);
+        brows, w.matched, &w.sp->j, out_p, out_b, out_cap);
     HIP_TRY(hipGetLastError());
   }
-  joink_sp hsp;
-  HIP_TRY(hipMemcpyAsync(&hsp, w.sp, sizeof(hsp), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  *out_nrows = (int64_t)hsp.j.cursor;
-  if ((int64_t)hsp.j.cursor > out_cap)
-    FAIL(GPUQ_ERR_OVERFLOW, "join_keys unmatched: %lld rows exceed out_cap %lld",
-         (long long)hsp.j.cursor, (long long)out_cap);
-  return GPUQ_OK;
+  return join_read_count(s, &w.sp->j, "join_keys unmatched", "rows", out_cap,
+                         out_nrows);
 }
 
 /* ---- partitioned aggregation (mid/high cardinality) ----
@@ -5229,47 +5092,50 @@ struct pred_args {
   gpuq_pred_insn insn[GPUQ_PRED_MAX_INSNS];
 };
 
-/* Row r of thread t is base + r * PRED_BLOCK + t: for each r a wave covers 64
- * consecutive rows, so its ballot is mask word r * PRED_WAVES + wave of the
- * tile and the words ascend in row order. The program counter is the same in
- * every lane (the program comes from the kernel arguments), so the
- * interpreter's branches are wave-uniform. Instructions outer, the 8 rows
- * inner and unrolled: a leaf issues its 8 loads back to back.
+static void pred_fill_args(pred_args* a, const gpuq_col* cols, int32_t ncols,
+                           const gpuq_pred_insn* prog, int32_t ninsns) {
+  memset(a, 0, sizeof(*a));
+  for (int c = 0; c < ncols; c++) {
+    a->data[c] = cols[c].data;
+    a->validity[c] = cols[c].validity;
+    a->dtype[c] = cols[c].dtype;
+  }
+  for (int pc = 0; pc < ninsns; pc++) a->insn[pc] = prog[pc];
+  a->ninsns = ninsns;
+}
+
+/* The interpreter: runs a validated program (pred_check_program: it never
+ * pops an empty stack) for R rows per thread and leaves row r's result in
+ * bit 0 of tb[r]. load(c, v) fetches column c for the thread's R rows: the
+ * values into v[], the validity bits (bit r = row r) as its result.
+ *
+ * The program counter is the same in every lane (the program comes from the
+ * kernel arguments), so the interpreter's branches are wave-uniform.
+ * Instructions outer, the R rows inner and unrolled: a leaf issues its R
+ * loads back to back.
  *
  * The per-row evaluation stack is two 32-bit words: bit d of tb[r] / nb[r] is
  * the TRUE / NULL flag of stack slot d (slot 0 = top; never both set; both
  * clear = FALSE). A push shifts left and ors the new flag in; AND / OR / NOT
  * rewrite the low bits. Nothing is indexed by a runtime value.
  *
- * cv / cvalid cache the most recently loaded col_a (8 values and validity
- * bits per thread): consecutive leaves on one column — BETWEEN, IN — load it
- * once. */
-__global__ __launch_bounds__(PRED_BLOCK)
-void k_pred_mask(int64_t n, pred_args a, unsigned long long* mask, uint32_t* cnt) {
-  __shared__ uint32_t wcnt[PRED_WAVES];
-  const int64_t base = (int64_t)blockIdx.x * PRED_TILE + threadIdx.x;
-  uint32_t tb[PRED_ITEMS], nb[PRED_ITEMS];
-  uint64_t cv[PRED_ITEMS];
+ * cv / cvalid cache the most recently loaded col_a: consecutive leaves on one
+ * column — BETWEEN, IN — load it once. */
+template <int R, class Load>
+DEV void pred_eval(const pred_args& a, Load load, uint32_t (&tb)[R]) {
+  uint32_t nb[R];
+  uint64_t cv[R];
   uint32_t cvalid = 0;
   int cached = -1;
   #pragma unroll
-  for (int r = 0; r < PRED_ITEMS; r++) { tb[r] = 0; nb[r] = 0; cv[r] = 0; }
+  for (int r = 0; r < R; r++) { tb[r] = 0; nb[r] = 0; cv[r] = 0; }
 
   for (int pc = 0; pc < a.ninsns; pc++) {
     const int opcode = a.insn[pc].opcode;
     if (opcode <= GPUQ_PRED_IS_NOT_NULL) {
       const int ca = a.insn[pc].col_a;
       if (ca != cached) {
-        const uint64_t* d = (const uint64_t*)a.data[ca];
-        const uint8_t* v = a.validity[ca];
-        cvalid = 0;
-        #pragma unroll
-        for (int r = 0; r < PRED_ITEMS; r++) {
-          int64_t i = base + r * PRED_BLOCK;
-          bool in = i < n;
-          cv[r] = in ? d[i] : 0;
-          cvalid |= (uint32_t)(in && bit_valid(v, i)) << r;
-        }
+        cvalid = load(ca, cv);
         cached = ca;
       }
       if (opcode == GPUQ_PRED_CMP_LIT) {
@@ -5277,7 +5143,7 @@ void k_pred_mask(int64_t n, pred_args a, unsigned long long* mask, uint32_t* cnt
         if (a.dtype[ca] == GPUQ_FLOAT64) {
           const double lit = a.insn[pc].lit_f64;
           #pragma unroll
-          for (int r = 0; r < PRED_ITEMS; r++) {
+          for (int r = 0; r < R; r++) {
             uint32_t ok = (cvalid >> r) & 1;
             uint32_t t = filter_cmp_f64(__longlong_as_double((long long)cv[r]), op, lit);
             tb[r] = (tb[r] << 1) | (t & ok);
@@ -5286,7 +5152,7 @@ void k_pred_mask(int64_t n, pred_args a, unsigned long long* mask, uint32_t* cnt
         } else {
           const int64_t lit = a.insn[pc].lit_i64;
           #pragma unroll
-          for (int r = 0; r < PRED_ITEMS; r++) {
+          for (int r = 0; r < R; r++) {
             uint32_t ok = (cvalid >> r) & 1;
             uint32_t t = filter_cmp_i64((int64_t)cv[r], op, lit);
             tb[r] = (tb[r] << 1) | (t & ok);
@@ -5295,22 +5161,11 @@ void k_pred_mask(int64_t n, pred_args a, unsigned long long* mask, uint32_t* cnt
         }
       } else if (opcode == GPUQ_PRED_CMP_COL) {
         const int op = a.insn[pc].cmp;
-        const int cb = a.insn[pc].col_b;
-        const uint64_t* d = (const uint64_t*)a.data[cb];
-        const uint8_t* v = a.validity[cb];
         const bool f64 = a.dtype[ca] == GPUQ_FLOAT64;
-        uint64_t bv[PRED_ITEMS];
-        uint32_t bvalid = 0;
+        uint64_t bv[R];
+        const uint32_t bvalid = load(a.insn[pc].col_b, bv) & cvalid;
         #pragma unroll
-        for (int r = 0; r < PRED_ITEMS; r++) {
-          int64_t i = base + r * PRED_BLOCK;
-          bool in = i < n;
-          bv[r] = in ? d[i] : 0;
-          bvalid |= (uint32_t)(in && bit_valid(v, i)) << r;
-        }
-        bvalid &= cvalid;
-        #pragma unroll
-        for (int r = 0; r < PRED_ITEMS; r++) {
+        for (int r = 0; r < R; r++) {
           uint32_t ok = (bvalid >> r) & 1;
           uint32_t t = f64
               ? filter_cmp_f64(__longlong_as_double((long long)cv[r]), op,
@@ -5322,7 +5177,7 @@ void k_pred_mask(int64_t n, pred_args a, unsigned long long* mask, uint32_t* cnt
       } else {   /* IS_NULL / IS_NOT_NULL */
         const uint32_t flip = opcode == GPUQ_PRED_IS_NULL ? 1u : 0u;
         #pragma unroll
-        for (int r = 0; r < PRED_ITEMS; r++) {
+        for (int r = 0; r < R; r++) {
           tb[r] = (tb[r] << 1) | (((cvalid >> r) & 1) ^ flip);
           nb[r] = nb[r] << 1;
         }
@@ -5331,13 +5186,13 @@ void k_pred_mask(int64_t n, pred_args a, unsigned long long* mask, uint32_t* cnt
       const uint32_t t = a.insn[pc].cmp == GPUQ_PRED_TRUE;
       const uint32_t nl = a.insn[pc].cmp == GPUQ_PRED_NULL;
       #pragma unroll
-      for (int r = 0; r < PRED_ITEMS; r++) {
+      for (int r = 0; r < R; r++) {
         tb[r] = (tb[r] << 1) | t;
         nb[r] = (nb[r] << 1) | nl;
       }
     } else if (opcode == GPUQ_PRED_AND) {
       #pragma unroll
-      for (int r = 0; r < PRED_ITEMS; r++) {
+      for (int r = 0; r < R; r++) {
         uint32_t T = tb[r], N = nb[r];
         uint32_t rt = (T >> 1) & T & 1;
         /* NULL unless a side is FALSE: both sides TRUE-or-NULL, one NULL */
@@ -5347,7 +5202,7 @@ void k_pred_mask(int64_t n, pred_args a, unsigned long long* mask, uint32_t* cnt
       }
     } else if (opcode == GPUQ_PRED_OR) {
       #pragma unroll
-      for (int r = 0; r < PRED_ITEMS; r++) {
+      for (int r = 0; r < R; r++) {
         uint32_t T = tb[r], N = nb[r];
         uint32_t rt = ((T >> 1) | T) & 1;
         uint32_t rn = ((N >> 1) | N) & ~rt & 1;
@@ -5356,10 +5211,34 @@ void k_pred_mask(int64_t n, pred_args a, unsigned long long* mask, uint32_t* cnt
       }
     } else {   /* NOT: FALSE <-> TRUE, NULL stays */
       #pragma unroll
-      for (int r = 0; r < PRED_ITEMS; r++)
+      for (int r = 0; r < R; r++)
         tb[r] = (tb[r] & ~1u) | (~(tb[r] | nb[r]) & 1);
     }
   }
+}
+
+/* Row r of thread t is base + r * PRED_BLOCK + t: for each r a wave covers 64
+ * consecutive rows, so its ballot is mask word r * PRED_WAVES + wave of the
+ * tile and the words ascend in row order. */
+__global__ __launch_bounds__(PRED_BLOCK)
+void k_pred_mask(int64_t n, pred_args a, unsigned long long* mask, uint32_t* cnt) {
+  __shared__ uint32_t wcnt[PRED_WAVES];
+  const int64_t base = (int64_t)blockIdx.x * PRED_TILE + threadIdx.x;
+  uint32_t tb[PRED_ITEMS];
+  pred_eval<PRED_ITEMS>(a, [&](int c, uint64_t (&v)[PRED_ITEMS]) {
+    const uint64_t* d = (const uint64_t*)a.data[c];
+    const uint8_t* val = a.validity[c];
+    uint32_t valid = 0;
+    #pragma unroll
+    for (int r = 0; r < PRED_ITEMS; r++) {
+      int64_t i = base + r * PRED_BLOCK;
+      bool in = i < n;
+      v[r] = in ? d[i] : 0;
+      valid |= (uint32_t)(in && bit_valid(val, i)) << r;
+    }
+    return valid;
+  }, tb);
+
 
   const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
   uint32_t total = 0;
@@ -5512,14 +5391,7 @@ extern "C" int gpuq_filter_expr(void* stream, int64_t n,
     FAIL(GPUQ_ERR_INVALID, "filter_expr: %d instructions, need 1..%d", ninsns, GPUQ_PRED_MAX_INSNS);
   if (int rc = pred_check_program("filter_expr", cols, ncols, prog, ninsns)) return rc;
   pred_args a;
-  memset(&a, 0, sizeof(a));
-  for (int c = 0; c < ncols; c++) {
-    a.data[c] = cols[c].data;
-    a.validity[c] = cols[c].validity;
-    a.dtype[c] = cols[c].dtype;
-  }
-  for (int pc = 0; pc < ninsns; pc++) a.insn[pc] = prog[pc];
-  a.ninsns = ninsns;
+  pred_fill_args(&a, cols, ncols, prog, ninsns);
   pred_ws w; int64_t need;
   pred_ws_layout(n, &w, (char*)workspace, &need);
   if (workspace_bytes < need)
@@ -5547,15 +5419,9 @@ extern "C" int gpuq_filter_expr(void* stream, int64_t n,
  * (gpuq_join_probe_keys_cond; it sits here, not beside k_joink_probe, because
  * it interprets the predicate program defined above.)
  *
- * k_joink_probe's two phases over the same table, with "match" narrowed to
- * "candidate for which the program is TRUE": phase A walks each probe row's
- * chain, evaluates the program on every (probe row, build row) candidate,
- * counts the passing ones and keeps the first two passing build rows in
- * c0 / c1; one output reservation per block; phase B emits, and for a row
- * with more than two passing pairs walks the rest of its chain again, from
- * next[c1] on, re-evaluating the program. Both walks follow next[] over an
- * immutable table and read the same columns, so phase B finds exactly the
- * cnt - 2 passing candidates phase A counted after c1.
+ * k_joink_probe with "match" narrowed to "candidate for which the program is
+ * TRUE": the skeleton's accept functor evaluates the program on every (probe
+ * row, build row) candidate, in phase A and again in phase B's walk past c1.
  *
  * Blocks own JOINC_CHUNK = 1024 rows (4 rounds), not JOIN_CHUNK: the rounds
  * are unrolled so that cnt / c0 / c1 stay in registers, and each round now
@@ -5564,13 +5430,11 @@ extern "C" int gpuq_filter_expr(void* stream, int64_t n,
  *
  * The program and the column table arrive by value in the kernel arguments,
  * so the program counter and every column index are wave-uniform even though
- * the lanes of a wave sit at different depths of different chains. The
- * evaluation stack is k_pred_mask's pair of bit words, and nothing is
- * indexed by a runtime value. A leaf loads its operand for the pair at hand:
- * a build-side column at the build row (one random 8-byte load), a
- * probe-side column at the probe row (coalesced across the wave, and served
- * by the L1 from the row's second candidate on). A one-entry cache makes the
- * leaves of an IN / BETWEEN on one column load it once per candidate.
+ * the lanes of a wave sit at different depths of different chains. A leaf
+ * loads its operand for the pair at hand: a build-side column at the build
+ * row (one random 8-byte load), a probe-side column at the probe row
+ * (coalesced across the wave, and served by the L1 from the row's second
+ * candidate on).
  * Holding the probe-side operands of a row in registers instead was tried:
  * with up to GPUQ_PRED_MAX_COLS columns they form an array that a leaf has
  * to pick from by its (uniform, but runtime) column index, which the
@@ -5579,190 +5443,52 @@ extern "C" int gpuq_filter_expr(void* stream, int64_t n,
 #define JOINC_CHUNK 1024
 
 struct joinc_args {
-  const void* data[GPUQ_PRED_MAX_COLS];
-  const uint8_t* validity[GPUQ_PRED_MAX_COLS];
-  int32_t dtype[GPUQ_PRED_MAX_COLS];
+  pred_args p;
   int32_t side[GPUQ_PRED_MAX_COLS];   /* GPUQ_JOIN_SIDE_* */
-  int32_t ncols;
-  int32_t ninsns;
-  gpuq_pred_insn insn[GPUQ_PRED_MAX_INSNS];
 };
 
-/* column c's value and validity for the pair (probe row i, build row b); the
- * side is wave-uniform, the row index a select between two registers */
-DEV void joinc_operand(const joinc_args& a, int64_t i, unsigned int b, int c,
-                       uint64_t* x, uint32_t* ok) {
-  const int64_t row = a.side[c] == GPUQ_JOIN_SIDE_BUILD ? (int64_t)b : i;
-  *x = ((const uint64_t*)a.data[c])[row];
-  *ok = bit_valid(a.validity[c], row);
-}
-
-DEV uint32_t joinc_cmp(int dtype, uint64_t x, int op, uint64_t y) {
-  return dtype == GPUQ_FLOAT64
-      ? filter_cmp_f64(__longlong_as_double((long long)x), op,
-                       __longlong_as_double((long long)y))
-      : filter_cmp_i64((int64_t)x, op, (int64_t)y);
-}
-
 /* TRUE iff the program evaluates to TRUE for (probe row i, build row b).
- * Bit d of tb / nb is the TRUE / NULL flag of stack slot d, as in
- * k_pred_mask; the validated program never pops an empty stack. */
+ * Column c is read at the row of its side: the side is wave-uniform, the row
+ * index a select between two registers. */
 DEV bool joinc_pass(const joinc_args& a, int64_t i, unsigned int b) {
-  uint32_t tb = 0, nb = 0;
-  uint64_t cv = 0;
-  uint32_t cok = 0;
-  int cached = -1;
-  for (int pc = 0; pc < a.ninsns; pc++) {
-    const int opcode = a.insn[pc].opcode;
-    if (opcode <= GPUQ_PRED_IS_NOT_NULL) {
-      const int ca = a.insn[pc].col_a;
-      if (ca != cached) {
-        joinc_operand(a, i, b, ca, &cv, &cok);
-        cached = ca;
-      }
-      if (opcode == GPUQ_PRED_CMP_LIT) {
-        const uint64_t lit = a.dtype[ca] == GPUQ_FLOAT64
-            ? (uint64_t)__double_as_longlong(a.insn[pc].lit_f64)
-            : (uint64_t)a.insn[pc].lit_i64;
-        uint32_t t = joinc_cmp(a.dtype[ca], cv, a.insn[pc].cmp, lit);
-        tb = (tb << 1) | (t & cok);
-        nb = (nb << 1) | (cok ^ 1);
-      } else if (opcode == GPUQ_PRED_CMP_COL) {
-        uint64_t y; uint32_t yok;
-        joinc_operand(a, i, b, a.insn[pc].col_b, &y, &yok);
-        yok &= cok;
-        uint32_t t = joinc_cmp(a.dtype[ca], cv, a.insn[pc].cmp, y);
-        tb = (tb << 1) | (t & yok);
-        nb = (nb << 1) | (yok ^ 1);
-      } else {   /* IS_NULL / IS_NOT_NULL */
-        const uint32_t flip = opcode == GPUQ_PRED_IS_NULL ? 1u : 0u;
-        tb = (tb << 1) | (cok ^ flip);
-        nb = nb << 1;
-      }
-    } else if (opcode == GPUQ_PRED_CONST) {
-      tb = (tb << 1) | (uint32_t)(a.insn[pc].cmp == GPUQ_PRED_TRUE);
-      nb = (nb << 1) | (uint32_t)(a.insn[pc].cmp == GPUQ_PRED_NULL);
-    } else if (opcode == GPUQ_PRED_AND) {
-      uint32_t T = tb, N = nb;
-      uint32_t rt = (T >> 1) & T & 1;
-      /* NULL unless a side is FALSE: both sides TRUE-or-NULL, one NULL */
-      uint32_t rn = ((N >> 1) | N) & ((T >> 1) | (N >> 1)) & (T | N) & 1;
-      tb = ((T >> 1) & ~1u) | rt;
-      nb = ((N >> 1) & ~1u) | rn;
-    } else if (opcode == GPUQ_PRED_OR) {
-      uint32_t T = tb, N = nb;
-      uint32_t rt = ((T >> 1) | T) & 1;
-      uint32_t rn = ((N >> 1) | N) & ~rt & 1;
-      tb = ((T >> 1) & ~1u) | rt;
-      nb = ((N >> 1) & ~1u) | rn;
-    } else {   /* NOT: FALSE <-> TRUE, NULL stays */
-      tb = (tb & ~1u) | (~(tb | nb) & 1);
-    }
-  }
-  return tb & 1;
+  uint32_t tb[1];
+  pred_eval<1>(a.p, [&](int c, uint64_t (&v)[1]) {
+    const int64_t row = a.side[c] == GPUQ_JOIN_SIDE_BUILD ? (int64_t)b : i;
+    v[0] = ((const uint64_t*)a.p.data[c])[row];
+    return (uint32_t)bit_valid(a.p.validity[c], row);
+  }, tb);
+  return tb[0] & 1;
 }
 
-/* JT 0-4 as k_joink_probe. Semi / anti need only "does a pair pass", so
- * their chain walk stops at the first passing candidate. */
+/* JT 0-4 as k_joink_probe, with joinc_pass as the accept functor */
 template <int JT>
-__global__ __launch_bounds__(256)
+__global__ __launch_bounds__(JOIN_BLOCK)
 void k_joink_probe_cond(int64_t n, joink_cols kc, int nkeys, int sw,
                         const unsigned long long* slots, const unsigned int* next,
                         joink_sp* sp, int64_t cap_mask, joinc_args a,
                         uint32_t* out_p, uint32_t* out_b, int64_t out_cap,
                         unsigned long long* matched) {
-  constexpr int ROUNDS = JOINC_CHUNK / 256;
-  __shared__ unsigned long long block_base;
-  __shared__ uint32_t wtot[256 / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = threadIdx.x / WAVE;
-  const int64_t base = (int64_t)blockIdx.x * JOINC_CHUNK;
-
+  constexpr int ROUNDS = JOINC_CHUNK / JOIN_BLOCK;
+  const int64_t base = (int64_t)blockIdx.x * JOINC_CHUNK + threadIdx.x;
+  auto accept = [&](int64_t i, unsigned int b) { return joinc_pass(a, i, b); };
   uint32_t cnt[ROUNDS];
   unsigned int c0[ROUNDS], c1[ROUNDS];
   uint32_t lane_total = 0;
   #pragma unroll
   for (int r = 0; r < ROUNDS; r++) {
-    int64_t i = base + r * 256 + threadIdx.x;
-    unsigned int head = JOIN_NIL;
-    int64_t key[JOINK_MAX_KEYS];
-    uint32_t h; unsigned long long mysig;
-    if (i < n && joink_load(kc, nkeys, i, key, &h, &mysig)) {
-      uint64_t slot = h & (uint64_t)cap_mask;
-      /* bounded: a full table ends the walk after cap visits */
-      for (int64_t visits = 0; visits <= cap_mask; visits++) {
-        const unsigned long long* sl = slots + slot * sw;
-        unsigned long long cur = sl[0];
-        if (cur == JOINK_EMPTY) break;
-        if (cur == mysig) {
-          bool eq = true;
-#pragma unroll
-          for (int c = 0; c < JOINK_MAX_KEYS; c++)
-            if (c < nkeys) eq = eq && sl[2 + c] == (unsigned long long)key[c];
-          if (eq) { head = (unsigned int)sl[1]; break; }
-        }
-        slot = (slot + 1) & (uint64_t)cap_mask;
-      }
-    }
-    cnt[r] = 0; c0[r] = JOIN_NIL; c1[r] = JOIN_NIL;
-    /* a head without JOIN_MULTI is a one-candidate chain: next[] untouched */
-    const bool multi = head != JOIN_NIL && (head & JOIN_MULTI);
-    for (unsigned int b = head == JOIN_NIL ? JOIN_NIL : (head & ~JOIN_MULTI);
-         b != JOIN_NIL; b = multi ? next[b] : JOIN_NIL) {
-      if (!joinc_pass(a, i, b)) continue;
-      if (cnt[r] == 0) c0[r] = b; else if (cnt[r] == 1) c1[r] = b;
-      cnt[r]++;
-      if (JT == 4) atomicOr(&matched[b >> 6], 1ull << (b & 63));
-      if (JT == 2 || JT == 3) break;
-    }
+    const int64_t i = base + r * JOIN_BLOCK;
+    const unsigned int head =
+        i < n ? joink_find_head(kc, nkeys, sw, slots, cap_mask, i) : JOIN_NIL;
+    join_collect<JT>(head, i, next, matched, accept, &cnt[r], &c0[r], &c1[r]);
     if (JT == 0) lane_total += cnt[r];
     else if (i < n) lane_total += jt_emit_count(JT, cnt[r]);
   }
-  /* phase B: block-level reservation (emit order within the block is
-   * arbitrary — join output order is nondeterministic by contract) */
-  uint32_t incl = wave_inclusive_scan(lane_total);
-  if (lane == WAVE - 1) wtot[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t tot = 0;
-    for (int w = 0; w < 256 / WAVE; w++) {
-      uint32_t t = wtot[w]; wtot[w] = tot; tot += t;
-    }
-    block_base = tot ? atomicAdd(&sp->j.cursor, (unsigned long long)tot) : 0;
-  }
-  __syncthreads();
-  int64_t o = (int64_t)block_base + wtot[wave] + (incl - lane_total);
+  int64_t o = join_reserve(lane_total, &sp->j.cursor);
   #pragma unroll
   for (int r = 0; r < ROUNDS; r++) {
-    int64_t i = base + r * 256 + threadIdx.x;
-    if (JT != 0) {
-      if (i >= n || !jt_emit_count(JT, cnt[r])) continue;
-      if (JT == 2 || JT == 3 || cnt[r] == 0) {
-        /* semi/anti emit the probe row once; outer's row without a passing
-         * pair goes with NIL (NULL build columns downstream) */
-        if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = JOIN_NIL; }
-        o++;
-        continue;
-      }
-    }
-    if (!cnt[r]) continue;
-    if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = c0[r]; }
-    o++;
-    if (cnt[r] >= 2) {
-      if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = c1[r]; }
-      o++;
-    }
-    if (cnt[r] > 2) {
-      /* the candidates after c1, in phase A's order; o advances by the
-       * reserved cnt - 2 whatever the walk finds */
-      const int64_t o_end = o + (cnt[r] - 2);
-      for (unsigned int b = next[c1[r]]; b != JOIN_NIL && o < o_end; b = next[b]) {
-        if (!joinc_pass(a, i, b)) continue;
-        if (o < out_cap) { out_p[o] = (uint32_t)i; out_b[o] = b; }
-        o++;
-      }
-      o = o_end;
-    }
+    const int64_t i = base + r * JOIN_BLOCK;
+    join_emit_row<JT>(i, i < n, cnt[r], c0[r], c1[r], next, accept, o,
+                      out_p, out_b, out_cap);
   }
 }
 
@@ -5803,45 +5529,19 @@ extern "C" int gpuq_join_probe_keys_cond(void* stream, int64_t prows,
          GPUQ_PRED_MAX_INSNS);
   if (int rc = pred_check_program(who, cond_cols, ncond_cols, prog, ninsns)) return rc;
   joinc_args a;
-  memset(&a, 0, sizeof(a));
-  for (int c = 0; c < ncond_cols; c++) {
-    a.data[c] = cond_cols[c].data;
-    a.validity[c] = cond_cols[c].validity;
-    a.dtype[c] = cond_cols[c].dtype;
-    a.side[c] = cond_sides[c];
-  }
-  for (int pc = 0; pc < ninsns; pc++) a.insn[pc] = prog[pc];
-  a.ncols = ncond_cols;
-  a.ninsns = ninsns;
+  pred_fill_args(&a.p, cond_cols, ncond_cols, prog, ninsns);
+  memset(a.side, 0, sizeof(a.side));
+  for (int c = 0; c < ncond_cols; c++) a.side[c] = cond_sides[c];
   joink_ws w; int64_t need;
   joink_ws_layout(cap, brows, nkeys, &w, (char*)workspace, &need);
-  HIP_TRY(hipMemsetAsync(&w.sp->j.cursor, 0, 8, s));
-  if (prows > 0) {
-    int sw = joink_stride_words(nkeys);
-    dim3 jg((uint32_t)((prows + JOINC_CHUNK - 1) / JOINC_CHUNK));
-    hipEvent_t _pe = prof_begin(s);
-#define JKPC(JT) k_joink_probe_cond<JT><<<jg, 256, 0, s>>>( \
-        prows, kc, nkeys, sw, w.slots, w.next, w.sp, cap - 1, a, out_p, out_b, \
-        out_cap, w.matched)
-    switch (join_type) {
-      case 1: JKPC(1); break;
-      case 2: JKPC(2); break;
-      case 3: JKPC(3); break;
-      case 4: JKPC(4); break;
-      default: JKPC(0); break;
-    }
-#undef JKPC
-    prof_end("join_keys_probe_cond", s, _pe);
-    HIP_TRY(hipGetLastError());
-  }
-  joink_sp hsp;
-  HIP_TRY(hipMemcpyAsync(&hsp, w.sp, sizeof(hsp), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  *out_nmatches = (int64_t)hsp.j.cursor;
-  if ((int64_t)hsp.j.cursor > out_cap)
-    FAIL(GPUQ_ERR_OVERFLOW, "%s: %lld matches exceed out_cap %lld", who,
-         (long long)hsp.j.cursor, (long long)out_cap);
-  return GPUQ_OK;
+  int sw = joink_stride_words(nkeys);
+  dim3 jg((uint32_t)((prows + JOINC_CHUNK - 1) / JOINC_CHUNK));
+  if (int rc = join_launch_probe<4>(s, &w.sp->j, prows, join_type, "join_keys_probe_cond", [&](auto jt) {
+        k_joink_probe_cond<decltype(jt)::value><<<jg, JOIN_BLOCK, 0, s>>>(
+            prows, kc, nkeys, sw, w.slots, w.next, w.sp, cap - 1, a, out_p,
+            out_b, out_cap, w.matched);
+      })) return rc;
+  return join_read_count(s, &w.sp->j, who, "matches", out_cap, out_nmatches);
 }
 
 /* One int64 operation with Java long semantics (Spark non-ANSI): + - * wrap

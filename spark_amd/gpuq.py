@@ -467,6 +467,8 @@ def join_build(build_keys: torch.Tensor, capacity: int, workspace=None,
 
 
 def join_probe_workspace(probe_rows: int, device="cuda") -> torch.Tensor:
+    """The probe needs no workspace of its own any more: 0 bytes. join_probe
+    still takes probe_ws= and ignores it."""
     return torch.empty(lib().gpuq_join_probe_workspace_bytes(probe_rows),
                        dtype=torch.uint8, device=device)
 
